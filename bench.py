@@ -20,6 +20,12 @@ its own RCCL communicator, include/eg_hip.h): torch is imported only for its CPU
 the GPU.  The step is bracketed by a barrier + a device synchronisation of the library's stream
 (group.sync(), the eg_ctx_sync of every kernel the step queued) on both sides.
 
+A plain run sets up, warms up, times the steps and prints the line.  --full adds every other
+figure of the line, each from a run of its own outside the timed steps: the CPU port on a sample
+of the same ballots (cpu_baseline, vs_baseline), the modexp microbenchmark, the encryption rates
+(host-pointer, device-resident, constant-time); without it those fields are null.
+--dump-outputs DIR writes what the last timed step returned (dump_outputs()).
+
 Prints ONE JSON line (rank 0).  See DESIGN.md §6 for the roofline definition.
 """
 from __future__ import annotations
@@ -68,16 +74,22 @@ def parse(argv=None):
     ap.add_argument("--strict-rccl", type=int, choices=(0, 1), default=None,
                     help="1 = a rank that cannot open its RCCL communicator fails the run (non-zero exit) "
                          "instead of falling back to a host exchange; default 1 at --gpus N > 1 in RCCL mode")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline (--cpu-*), the "
+                         "modexp microbenchmark (--modexp-n) and the encryption rates (--ct-encrypt)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned (verdicts, tally, counts) as "
+                         "DIR/<name>.npy in float32 / float64 (rank 0)")
     ap.add_argument("--fb-window", type=int, default=22, help="fixed-base radix window bits for g and K")
-    ap.add_argument("--cpu-sample", type=int, default=1, help="run the CPU baseline (0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=1, help="--full: run the CPU baseline (0 = skip)")
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="target wall time of the CPU baseline sample")
     ap.add_argument("--cpu-threads", type=int, default=0, help="CPU baseline threads (0 = the affinity count)")
     ap.add_argument("--cpu-max-ballots", type=int, default=2000,
                     help="ballots rank 0 keeps on the host for the CPU baseline at N > 1")
     ap.add_argument("--modexp-n", type=int, default=1 << 20,
-                    help="modexp microbenchmark batch (SURVEY 8(d): 2^20; rank 0 only; 0 = skip)")
+                    help="--full: modexp microbenchmark batch (SURVEY 8(d): 2^20; rank 0 only; 0 = skip)")
     ap.add_argument("--ct-encrypt", type=int, default=1,
-                    help="also time the constant-time encryption mode (eg_ctx_set_ct_encrypt; 0 = skip)")
+                    help="--full: also time the constant-time encryption mode (eg_ctx_set_ct_encrypt; 0 = skip)")
     a = ap.parse_args(argv)
     if a.manifest is None:
         a.manifest = "large" if a.pipeline == "full" else "small"
@@ -162,6 +174,26 @@ def note(rank, msg):
         print(f"bench: {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_BYTES = 48 << 20  # --dump-outputs writes at most this much array data in all
+
+
+def dump_outputs(dirpath, arrays):
+    """--dump-outputs: the arrays the last timed step handed its caller, as DIR/<name>.npy.  Bytes
+    and verdict flags go out as float32 (exact for 0..255), counts as float64.  An array over its
+    share of DUMP_BYTES is cut to a fixed, seeded sample of its rows (first axis), in order."""
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    share = DUMP_BYTES // len(arrays)
+    rng = np.random.default_rng(20241015)
+    for name, x in arrays.items():
+        x = np.asarray(x)
+        dt = np.float64 if x.dtype.itemsize > 2 else np.float32
+        row = max(1, x[0].size) * np.dtype(dt).itemsize
+        if x.shape[0] * row > share:
+            x = x[np.sort(rng.choice(x.shape[0], size=max(1, share // row), replace=False))]
+        np.save(d / f"{name}.npy", x.astype(dt))
+
+
 def init_ranks(a):
     """-> (world, rank, device, dist): the host process group (gloo, CPU only) at N > 1."""
     from electionguard.launch import launched_world
@@ -240,7 +272,7 @@ def verify_tally(a, world, rank, local, dist):
     eb = batch_encryption(group, key, qbar, man, votes, sn, cn)  # the ballots the step verifies
     # The encryption rates are N = 1 figures (at N > 1 a rank keeps only its device copy).
     enc_s = None
-    if world == 1:
+    if world == 1 and a.full:
         for _ in range(2):  # host-pointer encryption rate: best of two warm calls (same nonces, same bytes)
             t = time.perf_counter()
             batch_encryption(group, key, qbar, man, votes, sn, cn)
@@ -251,7 +283,7 @@ def verify_tally(a, world, rank, local, dist):
     d_okc = group.device_buffer(nb * man.n_contests)
     d_tal = group.device_buffer(man.n_real * 2 * 512)
     enc_dev = enc_dev_ct = None
-    if world == 1:
+    if world == 1 and a.full:
         enc_dev = encrypt_device_rate(group, key, qbar, man, votes, sn, cn, d_cts, d_rp, d_cp)
         if a.ct_encrypt:  # constant-time mode (masked table scans, no secret-indexed address): same bytes
             group.ct_encrypt = True
@@ -262,12 +294,14 @@ def verify_tally(a, world, rank, local, dist):
     # rank 0 keeps a bounded host sample of its ballots for the CPU baseline (at N = 1 the whole
     # batch stays: the sample is sized from a calibration run); the other ranks keep none
     sample = eb if world == 1 else (eb.slice(0, min(nb, a.cpu_max_ballots)) if rank == 0 else None)
+    if not (a.full and a.cpu_sample > 0):
+        sample = None
     if sample is not None and world > 1:
         sample = type(eb)(sample.cts.copy(), sample.rproof.copy(), sample.cproof.copy())
     del eb, sn, cn
     # modexp/sec/GPU microbenchmark on rank 0, before the verify step so the verify
     # launches stay the last k_pow dispatches of the process (tools/prof_summary.py)
-    modexp = modexp_ubench(group, a.modexp_n, rank) if a.modexp_n > 0 and rank == 0 else None
+    modexp = modexp_ubench(group, a.modexp_n, rank) if a.full and a.modexp_n > 0 and rank == 0 else None
     xch = TallyExchange(group, dist, world, rank, exchange_mode(), fallback=not a.strict_rccl)
     ver = Verifier(group, key, qbar, man)
     final_tally = None
@@ -300,6 +334,10 @@ def verify_tally(a, world, rank, local, dist):
     el = max_over_ranks(dist, el)
     rccl_ranks = xch.rccl_ranks  # what RCCL itself reports (ncclCommCount), before the communicator closes
     xch.close()
+    if a.dump_outputs and rank == 0:  # the last step's verdicts (this rank's ballots) and the folded tally
+        dump_outputs(a.dump_outputs, {"ok_selections": d_oks.download().reshape(nb, man.nsel),
+                                      "ok_contests": d_okc.download().reshape(nb, man.n_contests),
+                                      "tally": final_tally})
 
     value = nb * world * a.steps / el
     out = line_common(a, world, el, value, kp, nb, man, "ballots verified+tallied/sec (node, 4096-bit group)",
@@ -327,7 +365,7 @@ def report(a, out, world, rank, dist, man, sample, qbar, K):
     cpu_baseline and vs_baseline at every N."""
     if world > 1:
         dist.barrier()
-    if rank == 0 and a.cpu_sample > 0 and sample is not None:
+    if rank == 0 and a.full and a.cpu_sample > 0 and sample is not None:
         out["cpu_baseline"] = cpu_baseline(a, man, sample, qbar, K)
         attach_ratio(out)
     return out
@@ -681,6 +719,15 @@ def full_pipeline(a, world, rank, local, dist, keep=None):
     if xch.note:
         out["config"]["exchange_note"] = xch.note
     attach_traffic(out)
+    if a.dump_outputs and rank == 0:  # the last step's results, and the head of the ballots it encrypted
+        nd = min(nb, 8)
+        dump_outputs(a.dump_outputs, {"counts": np.array([-1 if x is None else int(x) for x in counts], np.int64),
+                                      "tally": last["tally"],
+                                      "ok_selections": d_oks.download().reshape(nb, man.nsel),
+                                      "ok_contests": d_okc.download().reshape(nb, man.n_contests),
+                                      "ciphertexts_head": d_cts[0:nd].download(),
+                                      "selection_proofs_head": d_rp[0:nd].download(),
+                                      "contest_proofs_head": d_cp[0:nd].download()})
     tot = nb * world * a.steps
     out["phases"] = {
         "encrypt": {"s": round(phases["encrypt"], 3), "ballots_per_s": round(tot / phases["encrypt"], 1)},
@@ -694,7 +741,7 @@ def full_pipeline(a, world, rank, local, dist, keep=None):
         "counts_exact": True,
     }
     sample = None
-    if rank == 0 and a.cpu_sample > 0:
+    if rank == 0 and a.full and a.cpu_sample > 0:
         ns = min(nb, a.cpu_max_ballots)
         sample = (votes[:ns], sn[:ns], cn[:ns], d_cts[0:ns].download(), d_rp[0:ns].download(), d_cp[0:ns].download())
     if keep is not None:

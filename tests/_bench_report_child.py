@@ -20,7 +20,7 @@ from electionguard.ballot import EncryptedBallots, Manifest  # noqa: E402
 
 
 def main():
-    a = bench.parse(["--gpus", "2", "--contests", "2", "--selections", "2", "--cpu-seconds", "0.5"])
+    a = bench.parse(["--full", "--gpus", "2", "--contests", "2", "--selections", "2", "--cpu-seconds", "0.5"])
     world, rank, _, dist = bench.init_ranks(a)
     G = O.production_group()
     rng = random.Random(3)

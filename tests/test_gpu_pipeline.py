@@ -14,14 +14,14 @@ pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
 
 
-def test_full_pipeline_small_against_the_oracle():
+def test_full_pipeline_small_against_the_oracle(tmp_path):
     sys.path.insert(0, str(ROOT))
     import bench
     from eg_oracle_c import COracle
     from electionguard.core import constants as C
-    a = bench.parse(["--pipeline", "full", "--ballots", "257", "--contests", "3", "--selections", "4",
+    a = bench.parse(["--full", "--pipeline", "full", "--ballots", "257", "--contests", "3", "--selections", "4",
                      "--steps", "1", "--warmup", "1", "--fb-window", "12", "--cpu-seconds", "1",
-                     "--cpu-max-ballots", "257", "--modexp-n", "0"])
+                     "--cpu-max-ballots", "257", "--modexp-n", "0", "--dump-outputs", str(tmp_path)])
     keep = {}
     out = bench.full_pipeline(a, 1, 0, 0, None, keep=keep)
     man = keep["man"]
@@ -37,3 +37,12 @@ def test_full_pipeline_small_against_the_oracle():
     assert cb["kind"] == "port" and "reproduced the GPU's bytes" in cb["sample"] and out["vs_baseline"] > 0
     assert out["metric"].startswith("ballots encrypted+verified+tallied+decrypted/sec")
     assert out["config"]["pipeline"] == "full"
+    # --dump-outputs: the step's results and the head of the ballots it encrypted, as float arrays
+    dump = {f.stem: np.load(f) for f in tmp_path.glob("*.npy")}
+    assert dump["counts"].dtype == np.float64 and [int(x) for x in dump["counts"]] == [int(x) for x in keep["want"]]
+    assert np.array_equal(dump["tally"], keep["tally"]) and dump["tally"].dtype == np.float32
+    assert dump["ok_selections"].shape == (257, man.nsel) and dump["ok_selections"].all()
+    assert dump["ok_contests"].shape == (257, man.n_contests) and dump["ok_contests"].all()
+    assert np.array_equal(dump["ciphertexts_head"], keep["cts"][:8])
+    assert np.array_equal(dump["selection_proofs_head"], keep["rproof"][:8])
+    assert np.array_equal(dump["contest_proofs_head"], keep["cproof"][:8])

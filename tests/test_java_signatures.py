@@ -54,8 +54,3 @@ def test_checker_catches_a_broken_signature(mutation):
     assert bad != src, "mutation did not apply"
     fx = _fixture()
     assert J.compare(J.override_methods(bad), fx["DecryptingTrusteeIF"], fx["delegate_calls"]) != []
-
-
-@pytest.mark.skipif(not J.REF.exists(), reason="the reference checkout is not present")
-def test_fixture_is_current_with_the_reference():
-    assert J.make_fixture() == _fixture()

@@ -31,7 +31,7 @@ def run_percall(threads: int, nb: int) -> dict:
 
 def batch_rates() -> dict:
     """bench.py's configs[1] line (10k ballots, batch API): verify + tally and encryption rates."""
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-sample", "0",
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--cpu-sample", "0",
                         "--modexp-n", "0", "--ct-encrypt", "0"], capture_output=True, text=True, timeout=900)
     if r.returncode != 0:
         sys.exit(f"bench.py failed:\n{r.stderr[-2000:]}")

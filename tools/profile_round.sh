@@ -15,16 +15,16 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd "$ROOT"
 timeout -k 10 420 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv \
-  -- python3 bench.py $BENCH_ARGS > "$OUT/bench_trace.log" 2>&1
+  -- python3 bench.py --full $BENCH_ARGS > "$OUT/bench_trace.log" 2>&1
 echo "trace pass done"
 timeout -k 10 420 rocprofv3 --pmc FETCH_SIZE -d "$OUT/fetch" -o run --output-format csv \
-  -- python3 bench.py --cpu-sample 0 $BENCH_ARGS > "$OUT/bench_fetch.log" 2>&1
+  -- python3 bench.py --full --cpu-sample 0 $BENCH_ARGS > "$OUT/bench_fetch.log" 2>&1
 echo "fetch pass done"
 timeout -k 10 420 rocprofv3 --pmc WRITE_SIZE -d "$OUT/write" -o run --output-format csv \
-  -- python3 bench.py --cpu-sample 0 $BENCH_ARGS > "$OUT/bench_write.log" 2>&1
+  -- python3 bench.py --full --cpu-sample 0 $BENCH_ARGS > "$OUT/bench_write.log" 2>&1
 echo "write pass done"
 timeout -k 10 420 rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE \
   -d "$OUT/sq" -o run --output-format csv \
-  -- python3 bench.py --cpu-sample 0 $BENCH_ARGS > "$OUT/bench_sq.log" 2>&1
+  -- python3 bench.py --full --cpu-sample 0 $BENCH_ARGS > "$OUT/bench_sq.log" 2>&1
 echo "sq pass done"
 python3 tools/prof_summary.py --dir "$OUT" --tag "$TAG"

@@ -11,6 +11,6 @@ if [ "$NPROC" -gt 2 ]; then FBW=${FBW:-20}; else FBW=${FBW:-22}; fi
 mkdir -p "$ROOT/gpurun_out"
 cd "$ROOT"
 EG_DIST_BACKEND=gloo timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node "$NPROC" \
-  --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus "$NPROC" --steps 2 --warmup 1 --ballots 2000 \
+  --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus "$NPROC" --steps 2 --warmup 1 --ballots 2000 \
   --fb-window "$FBW" --modexp-n 65536 > "gpurun_out/rehearse_gloo$NPROC.log" 2>&1
 tail -2 "gpurun_out/rehearse_gloo$NPROC.log"
