@@ -13,8 +13,8 @@
 
 struct Pow16Consts;  // the modulus constants in the 16-lane element layout (device memory)
 
-// p, r2 = R^2 mod p, one = R mod p as little-endian 32-bit words (128, 129, 129 of them; R = 2^4176,
-// the same Montgomery radix as the 8-lane layout); n0 = -p^-1 mod 2^29; friendly = (n0 == 1)
+// p, r2 = R^2 mod p, one = R mod p as little-endian 32-bit words (128, 129, 129 of them; R = 2^(29 * kSteps)
+// = 2^4118, the same Montgomery radix as the 8-lane layout); n0 = -p^-1 mod 2^29; friendly = (n0 == 1)
 int pow16_consts_create(const uint32_t* p, const uint32_t* r2, const uint32_t* one, uint32_t n0, uint32_t friendly,
                         Pow16Consts** out, std::string* err);
 void pow16_consts_destroy(Pow16Consts* c);
