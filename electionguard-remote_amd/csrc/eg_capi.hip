@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/eg_hip.h"
+#include "../../include/eg_hip_manifest.h"
 #include "eg_kernels.hpp"
 #include "eg_pow16.h"
 
@@ -1223,6 +1224,7 @@ extern "C" int eg_ctx_profile_end(eg_ctx* c, double* ms, double* mm, double* sqr
 }
 
 #include "eg_capi_ballot.inc"
+#include "eg_capi_manifest.inc"
 #include "eg_capi_coalesce.inc"
 #include "eg_capi_comm.inc"
 

@@ -354,6 +354,23 @@ __global__ void __launch_bounds__(kBlock) k_contest_flags(const uint8_t* __restr
   out[i] = ok;
 }
 
+// k_contest_flags for a manifest of unequal contests: contest j = b * nc + k of ballot b owns the
+// len[k] selections from first[k] on (ballot b's selections start at b * nsel).
+__global__ void __launch_bounds__(kBlock) k_contest_flags_seg(const uint8_t* __restrict__ sel_flags, uint32_t ncn,
+                                                              uint32_t nc, uint32_t nsel,
+                                                              const uint32_t* __restrict__ first,
+                                                              const uint32_t* __restrict__ len,
+                                                              uint8_t* __restrict__ out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= ncn * 2) return;
+  const uint32_t j = i >> 1, b = j / nc, k = j % nc;
+  const size_t base = ((size_t)b * nsel + first[k]) * 2 + (i & 1u);
+  const uint32_t n = len[k];
+  uint8_t ok = 1;
+  for (uint32_t s = 0; s < n; ++s) ok &= sel_flags[base + (size_t)s * 2];
+  out[i] = ok;
+}
+
 // out[i*so] = a[i*sa] * b[i*sb]  (Montgomery form; strides in elements)
 template <bool F>
 __global__ void __launch_bounds__(kBlock) k_mul(const MontConsts* __restrict__ C,
@@ -764,6 +781,48 @@ __global__ void __launch_bounds__(kBlock) k_prod(const MontConsts* __restrict__ 
   if (gid < njobs) store_elem(out + (size_t)gid * kW, x);
 }
 
+// k_prod with the group base read from a device table, for groups a mixed-radix map cannot reach
+// (the contests of one size in a manifest of unequal contests, the real selections of such a
+// manifest):  offset(g) = tab[g % period] + (g / period) * period_stride
+// (tab == nullptr: g * period_stride, the contiguous partial products of a later tree pass).
+// The padding with the Montgomery one, the mask and the job -> (group, chunk) split are k_prod's.
+// otab (optional, single-chunk passes only): group g's product goes to element
+// otab[g % period] + (g / period) * ostride instead of element g (the contest aggregates of one
+// size class land in ballot-major contest order, where the export and the hash read them).
+template <bool F>
+__global__ void __launch_bounds__(kBlock) k_prod_tab(const MontConsts* __restrict__ C,
+                                                     const uint32_t* __restrict__ in,
+                                                     const uint32_t* __restrict__ tab, uint32_t period,
+                                                     uint32_t period_stride, uint32_t ngroups, uint32_t len,
+                                                     uint32_t stride, uint32_t chunk, uint32_t nchunk,
+                                                     uint32_t* __restrict__ out, const uint32_t* __restrict__ otab,
+                                                     uint32_t ostride, const uint8_t* __restrict__ mask) {
+  const uint32_t gid = group_id();
+  const uint32_t njobs = ngroups * nchunk;
+  const uint32_t jb = gid < njobs ? gid : njobs - 1;
+  const uint32_t g = jb / nchunk, c = jb % nchunk;
+  uint32_t* slot = group_slot();
+  Mont<F> M;
+  M.load(C);
+  uint32_t x[kL];
+  const uint32_t gp = g % period, gq = g / period;
+  const size_t base = tab ? (size_t)tab[gp] + (size_t)gq * period_stride : (size_t)g * period_stride;
+  const uint32_t k0 = c * chunk;
+  const bool in0 = k0 < len && (mask == nullptr || mask[k0] != 0);
+  load_elem(x, in0 ? in + (base + (size_t)k0 * stride) * kW : C->one);
+#pragma unroll 1
+  for (uint32_t k = 1; k < chunk; ++k) {
+    const uint32_t kk = k0 + k;
+    const bool use = kk < len && (mask == nullptr || mask[kk] != 0);
+    const uint32_t* E = use ? in + (base + (size_t)kk * stride) * kW : C->one;
+    mmul_g(M, x, slot, E);
+  }
+  if (gid < njobs) {
+    const size_t o = otab ? (size_t)otab[gp] + (size_t)gq * ostride : (size_t)gid;
+    store_elem(out + o * kW, x);
+  }
+}
+
 // ---------------------------------------------------------------------------------
 // Fixed-base table construction.
 // k_sqr_chain: one group; P[j] = base^(2^j), j = 0..count-1 (Montgomery form).
@@ -999,6 +1058,22 @@ __global__ void k_enc_rsum(const uint8_t* __restrict__ q_be, const uint8_t* __re
   st256(rsum + (size_t)j * 32, r);
 }
 
+// k_enc_rsum for a manifest of unequal contests: contest j = b * nc + k sums the len[k] selection
+// nonces R from selection b * nsel + first[k] on
+__global__ void k_enc_rsum_seg(const uint8_t* __restrict__ q_be, const uint8_t* __restrict__ nonces, uint32_t ncon,
+                               uint32_t nc, uint32_t nsel, const uint32_t* __restrict__ first,
+                               const uint32_t* __restrict__ len, uint8_t* __restrict__ rsum) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= ncon) return;
+  const U256 q = ld256(q_be);
+  const uint32_t b = j / nc, k = j % nc, n = len[k];
+  const size_t s0 = (size_t)b * nsel + first[k];
+  U256 r;
+  for (int w = 0; w < 8; ++w) r.w[w] = 0;
+  for (uint32_t s = 0; s < n; ++s) r = addmod256(r, ld256(nonces + ((s0 + s) * 4) * 32), q);
+  st256(rsum + (size_t)j * 32, r);
+}
+
 // Finish the range proofs: c_real = c - c_fake, v_real = u - c_real*R (plus: u + c_real*R); arrange by m.
 __global__ void k_enc_finish(const uint8_t* __restrict__ q_be, const uint8_t* __restrict__ votes,
                              const uint8_t* __restrict__ nonces, const uint8_t* __restrict__ chal, uint32_t n,
@@ -1064,12 +1139,10 @@ __global__ void k_response(const uint8_t* __restrict__ q_be, const uint8_t* __re
 // plus (EG_RESPONSE_PLUS, a = g^v X^-c): out[i] = L*c_i mod q, and the proof words in neg_mask
 // (the challenges the variable bases are raised to) are negated in place, so the same job tables
 // compute X^-c; the Fiat-Shamir check then reads the caller's unmodified proofs.
-__global__ void k_scalar_prep(const uint8_t* __restrict__ q_be, uint8_t* __restrict__ proofs,
-                              uint32_t n, uint32_t words_per, uint32_t neg_idx, uint32_t L,
-                              uint8_t* __restrict__ out, uint8_t* __restrict__ ok, uint32_t plus,
-                              uint32_t neg_mask) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
+__device__ __forceinline__ void scalar_prep_item(const uint8_t* __restrict__ q_be, uint8_t* __restrict__ proofs,
+                                                 uint32_t i, uint32_t words_per, uint32_t neg_idx, uint32_t L,
+                                                 uint8_t* __restrict__ out, uint8_t* __restrict__ ok, uint32_t plus,
+                                                 uint32_t neg_mask) {
   const U256 q = ld256(q_be);
   bool good = true;
   for (uint32_t k = 0; k < words_per; ++k) good &= lt256(ld256(proofs + ((size_t)i * words_per + k) * 32), q);
@@ -1088,6 +1161,27 @@ __global__ void k_scalar_prep(const uint8_t* __restrict__ q_be, uint8_t* __restr
   }
   st256(out + (size_t)i * 32, c);
   ok[i] = good ? 1 : 0;
+}
+
+__global__ void k_scalar_prep(const uint8_t* __restrict__ q_be, uint8_t* __restrict__ proofs,
+                              uint32_t n, uint32_t words_per, uint32_t neg_idx, uint32_t L,
+                              uint8_t* __restrict__ out, uint8_t* __restrict__ ok, uint32_t plus,
+                              uint32_t neg_mask) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  scalar_prep_item(q_be, proofs, i, words_per, neg_idx, L, out, ok, plus, neg_mask);
+}
+
+// the contest form for a manifest of unequal contests: item i (contest i % period of its ballot)
+// takes its selection limit L from Ltab[i % period]
+__global__ void k_scalar_prep_tab(const uint8_t* __restrict__ q_be, uint8_t* __restrict__ proofs,
+                                  uint32_t n, uint32_t words_per, uint32_t neg_idx,
+                                  const uint32_t* __restrict__ Ltab, uint32_t period,
+                                  uint8_t* __restrict__ out, uint8_t* __restrict__ ok, uint32_t plus,
+                                  uint32_t neg_mask) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  scalar_prep_item(q_be, proofs, i, words_per, neg_idx, Ltab[i % period], out, ok, plus, neg_mask);
 }
 
 // ---------------------------------------------------------------------------------

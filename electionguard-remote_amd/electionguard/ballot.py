@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import ctypes
 from dataclasses import dataclass
-from typing import Optional, Tuple
+from typing import List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -43,6 +43,107 @@ class Manifest:
     @property
     def n_real(self) -> int:
         return self.n_contests * self.n_selections
+
+    # what lets a Manifest stand wherever an ElectionManifest does
+    @property
+    def contests(self) -> Tuple["Contest", ...]:
+        return (Contest(self.n_selections, self.votes_allowed),) * self.n_contests
+
+    @property
+    def offsets(self) -> np.ndarray:
+        return np.arange(self.n_contests, dtype=np.int64) * self.spc
+
+    @property
+    def real_index(self) -> np.ndarray:
+        return (self.offsets[:, None] + np.arange(self.n_selections, dtype=np.int64)[None, :]).reshape(-1)
+
+    @property
+    def max_votes_allowed(self) -> int:
+        return self.votes_allowed
+
+    @property
+    def spc_list(self) -> np.ndarray:
+        return np.full(self.n_contests, self.spc, dtype=np.uint32)
+
+    @property
+    def placeholders(self) -> np.ndarray:
+        return np.full(self.n_contests, self.votes_allowed, dtype=np.uint32)
+
+    @property
+    def limits(self) -> np.ndarray:
+        return self.placeholders
+
+
+@dataclass(frozen=True)
+class Contest:
+    """One contest of an ElectionManifest: n_selections real selections followed by
+    votes_allowed placeholder selections; its constant proof's limit is votes_allowed."""
+    n_selections: int
+    votes_allowed: int = 1
+
+    @property
+    def spc(self) -> int:
+        return self.n_selections + self.votes_allowed
+
+
+class ElectionManifest:
+    """A manifest whose contests differ in size (a vote-for-1 race among 3, a vote-for-3 board
+    race among 8, a yes/no measure).  Contest k's selections start at offsets[k] of a ballot's
+    nsel selections, its real selections first; real_index lists the real selections' positions
+    in tally order (contest-major).  Ballots of an ElectionManifest go through the
+    eg_*_ballots_manifest entry points (include/eg_hip_manifest.h)."""
+
+    def __init__(self, contests: Sequence[Union[Contest, Tuple[int, int]]]):
+        self.contests: Tuple[Contest, ...] = tuple(c if isinstance(c, Contest) else Contest(*c) for c in contests)
+        if not self.contests:
+            raise ValueError("a manifest needs at least one contest")
+        for c in self.contests:
+            if c.n_selections < 1 or c.votes_allowed < 0:
+                raise ValueError(f"bad contest {c}")
+        self.spc_list = np.array([c.spc for c in self.contests], dtype=np.uint32)
+        self.placeholders = np.array([c.votes_allowed for c in self.contests], dtype=np.uint32)
+        self.limits = self.placeholders.copy()
+        self.offsets = np.concatenate([[0], np.cumsum(self.spc_list.astype(np.int64))[:-1]]).astype(np.int64)
+        self.real_index = np.concatenate([o + np.arange(c.n_selections, dtype=np.int64)
+                                          for o, c in zip(self.offsets, self.contests)])
+
+    @property
+    def n_contests(self) -> int:
+        return len(self.contests)
+
+    @property
+    def nsel(self) -> int:
+        return int(self.spc_list.sum())
+
+    @property
+    def n_real(self) -> int:
+        return len(self.real_index)
+
+    @property
+    def max_votes_allowed(self) -> int:
+        return max(c.votes_allowed for c in self.contests)
+
+    def style(self, contest_indices: Sequence[int]) -> "ElectionManifest":
+        """The sub-manifest of a ballot style: the listed contests of this manifest, in the
+        order given.  A style's ballots are verified as their own batch and the per-style
+        tallies joined by merge_style_tallies."""
+        return ElectionManifest([self.contests[int(k)] for k in contest_indices])
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, ElectionManifest) and self.contests == other.contests
+
+    def __hash__(self) -> int:
+        return hash(self.contests)
+
+    def __repr__(self) -> str:
+        return f"ElectionManifest({[(c.n_selections, c.votes_allowed) for c in self.contests]})"
+
+
+AnyManifest = Union[Manifest, ElectionManifest]
+
+
+def _u32p(a: np.ndarray):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
 
 
 @dataclass
@@ -77,8 +178,18 @@ def random_scalars(rng: np.random.Generator, shape, q: int) -> np.ndarray:
         flat[ge] = rng.integers(0, 256, size=(int(ge.sum()), 32), dtype=np.uint8)
 
 
-def random_votes(rng: np.random.Generator, man: Manifest, nb: int) -> np.ndarray:
-    """One-hot vote over the real selections of each contest (placeholders 0)."""
+def random_votes(rng: np.random.Generator, man: AnyManifest, nb: int) -> np.ndarray:
+    """Manifest: one-hot vote over the real selections of each contest (placeholders 0).
+    ElectionManifest: per contest 0..votes_allowed distinct real selections voted, and as many
+    placeholders set as votes were left unused, so every contest sums to its limit."""
+    if isinstance(man, ElectionManifest):
+        v = np.zeros((nb, man.nsel), dtype=np.uint8)
+        for o, c in zip(man.offsets, man.contests):
+            for b in range(nb):
+                k = int(rng.integers(0, min(c.votes_allowed, c.n_selections) + 1))
+                v[b, o + rng.choice(c.n_selections, size=k, replace=False)] = 1
+                v[b, o + c.n_selections: o + c.n_selections + (c.votes_allowed - k)] = 1
+        return v
     v = np.zeros((nb, man.n_contests, man.spc), dtype=np.uint8)
     pick = rng.integers(0, man.n_selections, size=(nb, man.n_contests))
     np.put_along_axis(v, pick[..., None], 1, axis=2)
@@ -110,7 +221,7 @@ class ElectionKey:
                                                          self.window_bits))
 
 
-def batch_encryption(group: GroupContext, key: ElectionKey, qbar: int, man: Manifest, votes: np.ndarray,
+def batch_encryption(group: GroupContext, key: ElectionKey, qbar: int, man: AnyManifest, votes: np.ndarray,
                      sel_nonces: np.ndarray, contest_nonces: np.ndarray) -> EncryptedBallots:
     """Encrypt nb ballots with injected nonces (batchEncryption, RunRemoteWorkflowTest.java:140-141).
 
@@ -124,7 +235,13 @@ def batch_encryption(group: GroupContext, key: ElectionKey, qbar: int, man: Mani
     cts = np.empty((nb, man.nsel, 2, 512), dtype=np.uint8)
     rp = np.empty((nb, man.nsel, 4, 32), dtype=np.uint8)
     cp = np.empty((nb, man.n_contests, 2, 32), dtype=np.uint8)
-    if nb:
+    if nb and isinstance(man, ElectionManifest):
+        native.check(group._lib, "eg_encrypt_ballots_manifest",
+                     group._lib.eg_encrypt_ballots_manifest(group.handle, native.buf(key.K_be),
+                                                            native.buf(q_bytes(qbar)), nb, man.n_contests,
+                                                            _u32p(man.spc_list), _ptr(votes), _ptr(sn), _ptr(cn),
+                                                            _ptr(cts), _ptr(rp), _ptr(cp)))
+    elif nb:
         qb = q_bytes(qbar)
         native.check(group._lib, "eg_encrypt_ballots",
                      group._lib.eg_encrypt_ballots(group.handle, native.buf(key.K_be), native.buf(qb), nb,
@@ -133,12 +250,18 @@ def batch_encryption(group: GroupContext, key: ElectionKey, qbar: int, man: Mani
     return EncryptedBallots(cts, rp, cp)
 
 
-def batch_encryption_device(group: GroupContext, key: ElectionKey, qbar: int, man: Manifest, nb: int, d_votes: int,
+def batch_encryption_device(group: GroupContext, key: ElectionKey, qbar: int, man: AnyManifest, nb: int, d_votes: int,
                             d_sel_nonces: int, d_contest_nonces: int, d_cts: int, d_rproof: int,
                             d_cproof: int) -> None:
     """batch_encryption on device pointers (e.g. torch tensors' data_ptr()): the same
     layouts, inputs and outputs resident in HBM (eg_encrypt_ballots_dev)."""
-    if nb:
+    if nb and isinstance(man, ElectionManifest):
+        native.check(group._lib, "eg_encrypt_ballots_manifest_dev",
+                     group._lib.eg_encrypt_ballots_manifest_dev(group.handle, native.buf(key.K_be),
+                                                                native.buf(q_bytes(qbar)), nb, man.n_contests,
+                                                                _u32p(man.spc_list), d_votes, d_sel_nonces,
+                                                                d_contest_nonces, d_cts, d_rproof, d_cproof))
+    elif nb:
         native.check(group._lib, "eg_encrypt_ballots_dev",
                      group._lib.eg_encrypt_ballots_dev(group.handle, native.buf(key.K_be), native.buf(q_bytes(qbar)),
                                                        nb, man.n_contests, man.spc, d_votes, d_sel_nonces,
@@ -148,9 +271,13 @@ def batch_encryption_device(group: GroupContext, key: ElectionKey, qbar: int, ma
 class Verifier:
     """Ballot-proof verification + homomorphic tally (Verifier.verify / runAccumulateBallots)."""
 
-    def __init__(self, group: GroupContext, key: ElectionKey, qbar: int, man: Manifest):
+    def __init__(self, group: GroupContext, key: ElectionKey, qbar: int, man: AnyManifest):
         self.group, self.key, self.qbar, self.man = group, key, int(qbar), man
         self._qb = q_bytes(qbar)
+
+    def _shape_args(self):
+        man = self.man
+        return man.n_contests, _u32p(man.spc_list), _u32p(man.placeholders), _u32p(man.limits)
 
     def verify(self, eb: EncryptedBallots, with_tally: bool = True,
                cast: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
@@ -168,6 +295,13 @@ class Verifier:
         ok_s = np.zeros((nb, man.nsel), dtype=np.uint8)
         ok_c = np.zeros((nb, man.n_contests), dtype=np.uint8)
         tally = np.empty((man.n_real, 2, 512), dtype=np.uint8) if with_tally else None
+        if isinstance(man, ElectionManifest):
+            native.check(g._lib, "eg_verify_ballots_manifest",
+                         g._lib.eg_verify_ballots_manifest(g.handle, native.buf(self.key.K_be), native.buf(self._qb),
+                                                           nb, *self._shape_args(), _ptr(cts), _ptr(rp), _ptr(cp),
+                                                           _ptr(cm) if cm is not None else None, _ptr(ok_s),
+                                                           _ptr(ok_c), _ptr(tally) if tally is not None else None))
+            return ok_s.astype(bool), ok_c.astype(bool), tally
         native.check(g._lib, "eg_verify_ballots",
                      g._lib.eg_verify_ballots(g.handle, native.buf(self.key.K_be), native.buf(self._qb), nb,
                                               man.n_contests, man.spc, man.votes_allowed, man.votes_allowed, _ptr(cts),
@@ -180,13 +314,20 @@ class Verifier:
         """Asynchronous verify on device pointers (e.g. torch CUDA tensors' data_ptr()); d_cast
         (nb bytes, 0 = spoiled) as verify's cast."""
         man, g = self.man, self.group
+        if isinstance(man, ElectionManifest):
+            native.check(g._lib, "eg_verify_ballots_manifest_dev",
+                         g._lib.eg_verify_ballots_manifest_dev(g.handle, native.buf(self.key.K_be),
+                                                               native.buf(self._qb), nb, *self._shape_args(), d_cts,
+                                                               d_rproof, d_cproof, d_cast, d_ok_sel, d_ok_con,
+                                                               d_tally))
+            return
         native.check(g._lib, "eg_verify_ballots_dev",
                      g._lib.eg_verify_ballots_dev(g.handle, native.buf(self.key.K_be), native.buf(self._qb), nb,
                                                   man.n_contests, man.spc, man.votes_allowed, man.votes_allowed, d_cts,
                                                   d_rproof, d_cproof, d_cast, d_ok_sel, d_ok_con, d_tally))
 
 
-def accumulate_tally(group: GroupContext, man: Manifest, eb: EncryptedBallots,
+def accumulate_tally(group: GroupContext, man: AnyManifest, eb: EncryptedBallots,
                      cast: Optional[np.ndarray] = None) -> np.ndarray:
     """runAccumulateBallots without verification: per real selection, prod pad / prod data over the
     cast ballots (cast (nb,) bool, None = all)."""
@@ -194,8 +335,29 @@ def accumulate_tally(group: GroupContext, man: Manifest, eb: EncryptedBallots,
         eb = EncryptedBallots(eb.cts[np.asarray(cast, bool)], eb.rproof[np.asarray(cast, bool)],
                               eb.cproof[np.asarray(cast, bool)])
     nb = eb.n
-    sel = eb.cts.reshape(nb, man.n_contests, man.spc, 2, 512)[:, :, : man.n_selections]
+    sel = eb.cts.reshape(nb, man.nsel, 2, 512)[:, man.real_index]
     # groups ordered (contest, selection, component), elements over ballots
-    g = np.ascontiguousarray(np.transpose(sel, (1, 2, 3, 0, 4))).reshape(-1, 512)
+    g = np.ascontiguousarray(np.transpose(sel, (1, 2, 0, 3))).reshape(-1, 512)
     out = group.prodP_groups(g, man.n_real * 2, nb)
     return out.reshape(man.n_real, 2, 512)
+
+
+def merge_style_tallies(group: GroupContext, man: ElectionManifest,
+                        parts: Sequence[Tuple[Sequence[int], np.ndarray]]) -> np.ndarray:
+    """Join per-style tallies into the full manifest's (n_real, 2, 512) tally.  parts holds, per
+    ballot style, the contest indices given to man.style() and the tally of that style's batch;
+    a contest's selections are multiplied over every style that carries it (multP_batch), and
+    contests that no style covers stay 1 (the empty product)."""
+    real_off = np.concatenate([[0], np.cumsum([c.n_selections for c in man.contests])]).astype(np.int64)
+    out = np.zeros((man.n_real, 2, 512), dtype=np.uint8)
+    out[:, :, 511] = 1
+    for contest_indices, tally in parts:
+        rows = np.concatenate([np.arange(real_off[int(k)], real_off[int(k) + 1]) for k in contest_indices]) \
+            if len(contest_indices) else np.zeros(0, np.int64)
+        t = np.ascontiguousarray(tally, dtype=np.uint8).reshape(-1, 2, 512)
+        if t.shape[0] != len(rows):
+            raise ValueError(f"style {list(contest_indices)} has {len(rows)} real selections, its tally {t.shape[0]}")
+        if len(rows):
+            prod = group.multP_batch(np.ascontiguousarray(out[rows]).reshape(-1, 512), t.reshape(-1, 512))
+            out[rows] = np.asarray(prod).reshape(-1, 2, 512)
+    return out

@@ -33,6 +33,13 @@ EXPORTED = [
 ]
 
 
+# Every symbol declared in include/eg_hip_manifest.h (manifests of unequal contests).
+EXPORTED_MANIFEST = [
+    "eg_verify_ballots_manifest", "eg_verify_ballots_manifest_dev",
+    "eg_encrypt_ballots_manifest", "eg_encrypt_ballots_manifest_dev",
+]
+
+
 class NativeUnavailable(RuntimeError):
     pass
 
@@ -56,6 +63,7 @@ def _sig(lib: ctypes.CDLL) -> None:
     S = c_sz
     U32 = ctypes.c_uint32
     D = ctypes.POINTER(ctypes.c_double)
+    U32P = ctypes.POINTER(U32)
     sigs = {
         "eg_last_error": ([], ctypes.c_char_p),
         "eg_version": ([ctypes.c_char_p, S], I),
@@ -111,6 +119,10 @@ def _sig(lib: ctypes.CDLL) -> None:
         "eg_fb_pow_submit": ([P, P, P, ctypes.POINTER(c_vp)], I),
         "eg_fb_pow_one": ([P, P, P], I),
         "eg_ctx_set_ct_pow": ([P, I], I),
+        "eg_verify_ballots_manifest": ([P, P, P, S, S, U32P, U32P, U32P, P, P, P, P, P, P, P], I),
+        "eg_verify_ballots_manifest_dev": ([P, P, P, S, S, U32P, U32P, U32P, P, P, P, P, P, P, P], I),
+        "eg_encrypt_ballots_manifest": ([P, P, P, S, S, U32P, P, P, P, P, P, P], I),
+        "eg_encrypt_ballots_manifest_dev": ([P, P, P, S, S, U32P, P, P, P, P, P, P], I),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name)

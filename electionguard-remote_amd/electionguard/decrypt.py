@@ -375,7 +375,7 @@ def spoiled_texts(man, cts: np.ndarray) -> np.ndarray:
     """The real selections' ciphertexts of spoiled ballots, ballot-major: (nb * n_real, 2, 512)
     from the wire layout (nb, nsel, 2, 512) (placeholders are not part of a decrypted ballot)."""
     nb = cts.shape[0]
-    sel = np.asarray(cts).reshape(nb, man.n_contests, man.spc, 2, 512)[:, :, : man.n_selections]
+    sel = np.asarray(cts).reshape(nb, man.nsel, 2, 512)[:, man.real_index]
     return np.ascontiguousarray(sel).reshape(nb * man.n_real, 2, 512)
 
 
@@ -440,9 +440,9 @@ class Decryption:
         """decryptBallot over a batch of spoiled ballots keeping every share and proof: the texts
         are the ballots' real selections, ballot-major, in ONE trustee batch per guardian (and
         per missing guardian), so the record's counts are the plaintext selections in that
-        order, each in [0, votesAllowed]."""
+        order, each in [0, votesAllowed] (an ElectionManifest's largest votes_allowed)."""
         cts = ballots.cts if hasattr(ballots, "cts") else np.asarray(ballots)
-        return self.decrypt_record(spoiled_texts(man, cts), man.votes_allowed)
+        return self.decrypt_record(spoiled_texts(man, cts), man.max_votes_allowed)
 
     def decryptBallots(self, ballots, man) -> np.ndarray:
         """-> (nb, n_real) decrypted selections of the spoiled ballots (EncryptedBallots or their

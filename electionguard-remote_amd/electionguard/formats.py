@@ -13,6 +13,7 @@ both; the two hex forms hash the same text unless a hashed element has a leading
 
 Record (JSON, hex strings; tools/pin_format.py):
   {"K": ..., "qbar": ..., "manifest": [contests, selections, votes_allowed],
+                                       # or, for unequal contests, [[selections, votes_allowed], ...]
    "ballots": [{"cts": [[alpha, beta], ...], "rproofs": [[c0, v0, c1, v1], ...],
                 "cproofs": [[c, v], ...]}, ...],                      # optional
    "shares": [{"text": [pad, data], "key": K_i, "M": ..., "c": ..., "v": ...}, ...]}   # optional
@@ -33,12 +34,31 @@ def _h(s: str, n: int) -> np.ndarray:
     return np.frombuffer(bytes.fromhex(s).rjust(n, b"\0")[-n:], np.uint8)
 
 
+def record_manifest(rec: dict):
+    """The record's "manifest": three integers [contests, selections, votes_allowed] -> Manifest, a
+    list of [selections, votes_allowed] pairs (one per contest) -> ElectionManifest."""
+    from .ballot import ElectionManifest, Manifest
+    m = rec["manifest"]
+    if len(m) and all(isinstance(x, (list, tuple)) for x in m):
+        return ElectionManifest([(int(ns), int(va)) for ns, va in m])
+    nc, ns, va = m
+    return Manifest(int(nc), int(ns), int(va))
+
+
+def manifest_field(man) -> list:
+    """A manifest as the record's "manifest" field (the inverse of record_manifest)."""
+    from .ballot import ElectionManifest
+    if isinstance(man, ElectionManifest):
+        return [[c.n_selections, c.votes_allowed] for c in man.contests]
+    return [man.n_contests, man.n_selections, man.votes_allowed]
+
+
 def record_arrays(rec: dict):
     """-> (ballot arrays or None, share arrays or None) in the C ABI layouts."""
     ballots = shares = None
     if rec.get("ballots"):
-        nc, ns, va = rec["manifest"]
-        nsel = nc * (ns + va)
+        man = record_manifest(rec)
+        nc, nsel = man.n_contests, man.nsel
         bs = rec["ballots"]
         cts = np.stack([np.stack([_h(x, 512) for ct in b["cts"] for x in ct]).reshape(nsel, 2, 512) for b in bs])
         rp = np.stack([np.stack([_h(x, 32) for pr in b["rproofs"] for x in pr]).reshape(nsel, 4, 32) for b in bs])
@@ -58,7 +78,7 @@ def pin_formats(group, rec: dict) -> List[Dict]:
     """Verify the record's ballots and shares under every (hash form, response, pre-image order)
     on ``group``'s GPU; -> one entry per combination with the fraction of ballots and shares that
     verify (the context's settings are restored afterwards)."""
-    from .ballot import ElectionKey, EncryptedBallots, Manifest, Verifier
+    from .ballot import ElectionKey, EncryptedBallots, Verifier
     from .decrypt import verify_shares
 
     ballots, shares = record_arrays(rec)
@@ -66,8 +86,7 @@ def pin_formats(group, rec: dict) -> List[Dict]:
     saved = (group.hash_format, group.proof_format)
     V = None
     if ballots is not None:
-        nc, ns, va = rec["manifest"]
-        V = Verifier(group, ElectionKey(group, int(rec["K"], 16)), qbar, Manifest(nc, ns, va))
+        V = Verifier(group, ElectionKey(group, int(rec["K"], 16)), qbar, record_manifest(rec))
     out = []
     try:
         for hf, resp, pre in itertools.product(HASH_FORMATS, RESPONSES, PREIMAGES):

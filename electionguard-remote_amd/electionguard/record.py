@@ -26,7 +26,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .ballot import ElectionKey, EncryptedBallots, Manifest, Verifier
+from .ballot import AnyManifest, ElectionKey, EncryptedBallots, Manifest, Verifier  # noqa: F401
 from .core.group import GroupContext, as_p_array
 from .decrypt import DecryptionRecord, spoiled_texts, verify_decryption_record
 from .keyceremony import verify_commitment_proofs
@@ -42,7 +42,7 @@ class GuardianRecord:
 
 @dataclass
 class ElectionRecord:
-    manifest: Manifest
+    manifest: AnyManifest           # a uniform Manifest or an ElectionManifest
     qbar: int                       # extended base hash Q-bar
     joint_key: int                  # K
     guardians: List[GuardianRecord]
@@ -102,7 +102,7 @@ def verify_election_record(group: GroupContext, rec: ElectionRecord, window_bits
             sv = verify_decryption_record(group, rec.qbar, sp, pks, commitments,
                                           guardian_xs={g.gid: g.x for g in rec.guardians},
                                           quorum=len(rec.guardians[0].commitments) if shapes_ok else None,
-                                          max_count=man.votes_allowed)
+                                          max_count=man.max_votes_allowed)
             for name, ok in sv.items():
                 out[f"spoiled.{name}"] = ok
     return out
