@@ -30,7 +30,9 @@
 
 #include "../../include/eg_hip.h"
 #include "../../include/eg_hip_manifest.h"
+#include "../../include/eg_hip_codes.h"
 #include "eg_kernels.hpp"
+#include "eg_codes.hpp"
 #include "eg_pow16.h"
 
 using namespace eg;
@@ -1225,6 +1227,7 @@ extern "C" int eg_ctx_profile_end(eg_ctx* c, double* ms, double* mm, double* sqr
 
 #include "eg_capi_ballot.inc"
 #include "eg_capi_manifest.inc"
+#include "eg_capi_codes.inc"
 #include "eg_capi_coalesce.inc"
 #include "eg_capi_comm.inc"
 

@@ -40,6 +40,14 @@ EXPORTED_MANIFEST = [
 ]
 
 
+# Every symbol declared in include/eg_hip_codes.h (ballot nonces, ballot hashes, code chain).
+EXPORTED_CODES = [
+    "eg_derive_ballot_nonces", "eg_derive_ballot_nonces_dev",
+    "eg_ballot_hashes", "eg_ballot_hashes_dev",
+    "eg_verify_code_chain", "eg_verify_code_chain_dev",
+]
+
+
 class NativeUnavailable(RuntimeError):
     pass
 
@@ -123,6 +131,12 @@ def _sig(lib: ctypes.CDLL) -> None:
         "eg_verify_ballots_manifest_dev": ([P, P, P, S, S, U32P, U32P, U32P, P, P, P, P, P, P, P], I),
         "eg_encrypt_ballots_manifest": ([P, P, P, S, S, U32P, P, P, P, P, P, P], I),
         "eg_encrypt_ballots_manifest_dev": ([P, P, P, S, S, U32P, P, P, P, P, P, P], I),
+        "eg_derive_ballot_nonces": ([P, S, S, U32P, P, P, P], I),
+        "eg_derive_ballot_nonces_dev": ([P, S, S, U32P, P, P, P], I),
+        "eg_ballot_hashes": ([P, S, S, U32P, P, P, P, P, P, P, P, P], I),
+        "eg_ballot_hashes_dev": ([P, S, S, U32P, P, P, P, P, P, P, P, P], I),
+        "eg_verify_code_chain": ([P, S, P, P, P, P, P], I),
+        "eg_verify_code_chain_dev": ([P, S, P, P, P, P, P], I),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name)

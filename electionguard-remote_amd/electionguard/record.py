@@ -14,10 +14,13 @@ path produces.  Every exponentiation runs on the GPU through the C ABI:
   * ``spoiled.*``        with spoiled ballots (``cast`` flags): their decryption record covers
                          exactly their real selections (``spoiled.texts``) and passes the same
                          share / quorum / B == M g^t checks with values <= votesAllowed
-                         (decryptBallot, RunRemoteDecryptor.java:264-269).
+                         (decryptBallot, RunRemoteDecryptor.java:264-269);
+  * ``ballot_codes``     when the record carries confirmation codes: the device ballot hashes of
+                         ``ballots`` chain to ``codes`` from ``code_seed`` (ballot chaining;
+                         electionguard.codes, include/eg_hip_codes.h).
 
-Manifest, hash-chain and protobuf-format checks are record plumbing outside the hot path
- and are not restated.
+Manifest and protobuf-format checks are record plumbing outside the hot path and
+are not restated; the ballot hash chain is checked when the record carries it.
 """
 from __future__ import annotations
 
@@ -26,7 +29,9 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
+from . import codes as _codes
 from .ballot import AnyManifest, ElectionKey, EncryptedBallots, Manifest, Verifier  # noqa: F401
+from .codes import ManifestHashes
 from .core.group import GroupContext, as_p_array
 from .decrypt import DecryptionRecord, spoiled_texts, verify_decryption_record
 from .keyceremony import verify_commitment_proofs
@@ -51,6 +56,26 @@ class ElectionRecord:
     decryption: DecryptionRecord
     cast: Optional[np.ndarray] = None                   # (nb,) bool; None = every ballot cast
     spoiled_decryption: Optional[DecryptionRecord] = None  # the spoiled ballots' selections
+    # the confirmation-code chain (electionguard.codes); checked when codes is present
+    ballot_ids: Optional[np.ndarray] = None             # (nb, 32)
+    timestamps: Optional[np.ndarray] = None             # (nb, 32) elements, or nb integer seconds
+    code_seed: Optional[np.ndarray] = None              # 32 bytes (or an integer): code[-1]
+    codes: Optional[np.ndarray] = None                  # (nb, 32)
+    hashes: Optional[ManifestHashes] = None             # the manifest's description hashes
+
+
+def _codes_ok(group: GroupContext, rec: ElectionRecord) -> bool:
+    """The ballots' hashes, taken on the device, chain to the recorded codes (every ballot, cast
+    or spoiled: a spoiled ballot keeps its place in the chain)."""
+    nb = rec.ballots.n
+    if any(x is None for x in (rec.ballot_ids, rec.timestamps, rec.code_seed, rec.hashes)):
+        return False
+    try:
+        B = _codes.ballot_hashes(group, rec.manifest, rec.hashes, rec.ballot_ids, rec.ballots.cts)
+        ok = _codes.verify_code_chain(group, rec.code_seed, rec.timestamps, B, rec.codes)
+    except ValueError:  # wrong shapes
+        return False
+    return ok.shape == (nb,) and bool(ok.all())
 
 
 def verify_election_record(group: GroupContext, rec: ElectionRecord, window_bits: int = 8) -> Dict[str, bool]:
@@ -78,6 +103,8 @@ def verify_election_record(group: GroupContext, rec: ElectionRecord, window_bits
         cast = np.ones(nb, bool)
     ok_s, ok_c, tally = Verifier(group, key, rec.qbar, man).verify(rec.ballots, cast=cast)
     out["ballots"] = bool(ok_s.all() and ok_c.all()) and cast_ok
+    if rec.codes is not None:
+        out["ballot_codes"] = _codes_ok(group, rec)
     et = np.ascontiguousarray(rec.encrypted_tally, dtype=np.uint8).reshape(-1, 2, 512)
     out["tally"] = et.shape == tally.shape and bool(np.array_equal(et, tally))
     dtexts = np.ascontiguousarray(rec.decryption.texts, dtype=np.uint8).reshape(-1, 2, 512)
