@@ -48,6 +48,14 @@ EXPORTED_CODES = [
 ]
 
 
+# Every symbol declared in include/eg_hip_contestdata.h (contest data under HashedElGamal).
+EXPORTED_CONTEST_DATA = [
+    "eg_derive_contest_data_nonces", "eg_derive_contest_data_nonces_dev",
+    "eg_seal_contest_data", "eg_seal_contest_data_dev",
+    "eg_open_contest_data", "eg_open_contest_data_dev",
+]
+
+
 class NativeUnavailable(RuntimeError):
     pass
 
@@ -137,6 +145,12 @@ def _sig(lib: ctypes.CDLL) -> None:
         "eg_ballot_hashes_dev": ([P, S, S, U32P, P, P, P, P, P, P, P, P], I),
         "eg_verify_code_chain": ([P, S, P, P, P, P, P], I),
         "eg_verify_code_chain_dev": ([P, S, P, P, P, P, P], I),
+        "eg_derive_contest_data_nonces": ([P, S, S, P, P], I),
+        "eg_derive_contest_data_nonces_dev": ([P, S, S, P, P], I),
+        "eg_seal_contest_data": ([P, P, S, S, S, P, P, P, P, P, P], I),
+        "eg_seal_contest_data_dev": ([P, P, S, S, S, P, P, P, P, P, P], I),
+        "eg_open_contest_data": ([P, S, S, S, P, P, P, P, P, P, P], I),
+        "eg_open_contest_data_dev": ([P, S, S, S, P, P, P, P, P, P, P], I),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name)

@@ -31,6 +31,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import contest_data as _cd
 from .core import native
 from .core.group import GroupContext, as_p_array, as_q_array, p_bytes, q_bytes
 from .keyceremony import GuardianKeys, backup_label, backup_open, poly_eval
@@ -393,10 +394,11 @@ class Decryption:
         """tally: (n, 2, 512) encrypted per-selection totals -> plaintext counts."""
         return self.decrypt_record(tally, max_count).counts
 
-    def decrypt_record(self, tally: np.ndarray, max_count: int) -> DecryptionRecord:
-        """decrypt() keeping every share and proof (the published decryption record)."""
+    def _shares_and_combine(self, T: np.ndarray) -> Tuple[DecryptionRecord, np.ndarray]:
+        """Every trustee's shares of the texts T (n, 2, 512), each proof checked, and their combine
+        M (n, 512) = prod_i M_i * prod_l prod_i M_{l,i}^{w_i}: pad^s for the joint secret s.  The
+        record comes back without counts."""
         G = self.group
-        T = _texts_array(tally)
         n = len(T)
         xs = [t.xCoordinate() for t in self.trustees]
         rec = DecryptionRecord(T, {t.id(): t.xCoordinate() for t in self.trustees}, {}, {}, [])
@@ -430,10 +432,39 @@ class Decryption:
                 parts.append(G.powP_batch(Ml, [w] * n))
         k = len(parts)
         stacked = np.ascontiguousarray(np.stack(parts, axis=1)).reshape(n * k, 512)
-        M = G.prodP_groups(stacked, n, k)
+        return rec, G.prodP_groups(stacked, n, k)
+
+    def decrypt_record(self, tally: np.ndarray, max_count: int) -> DecryptionRecord:
+        """decrypt() keeping every share and proof (the published decryption record)."""
+        G = self.group
+        T = _texts_array(tally)
+        rec, M = self._shares_and_combine(T)
         Tv = G.multP_batch(np.ascontiguousarray(T[:, 1]), G.multInv_batch(M))
         rec.counts = dlog_g_batch(G, Tv, max_count)
         return rec
+
+    # ---- contest data: the HashedElGamal part of decryptBallot ----
+    def decryptContestData(self, c0, c1, c2, ballot_ids, ncontest: int) -> Tuple[np.ndarray, np.ndarray]:
+        """Open the contest data of spoiled ballots through the trustees -> (data (nb, nc, nbytes),
+        ok (nb, nc) bool); c0 (nb, nc, 512), c1 (nb, nc, nbytes), c2 (nb, nc, 32), ballot_ids
+        (nb, 32).  The texts handed to the trustees are (pad = c0, data = 1), so the direct and
+        compensated batch calls, their proofs and the gRPC proxies serve unchanged; kappa = c0^s
+        is the Lagrange-combined M (electionguard.contest_data).  A bad share raises, as in
+        decrypt_record; a bad MAC gives ok False and a zero row for that item only."""
+        G = self.group
+        ids = np.ascontiguousarray(ballot_ids, dtype=np.uint8).reshape(-1, 32)
+        nb = len(ids)
+        n = nb * ncontest
+        c1 = np.ascontiguousarray(c1, dtype=np.uint8)
+        if n == 0 or c1.size % n:
+            raise ValueError("c1: one row per (ballot, contest)")
+        nbytes = c1.size // n
+        T = np.zeros((n, 2, 512), dtype=np.uint8)
+        T[:, 0] = np.ascontiguousarray(c0, dtype=np.uint8).reshape(n, 512)
+        T[:, 1, 511] = 1
+        _, kappa = self._shares_and_combine(T)
+        data, ok = _cd.open_sealed(G, ncontest, nbytes, ids, T[:, 0], kappa, c1, c2)
+        return data.reshape(nb, ncontest, nbytes), ok.reshape(nb, ncontest)
 
     # ---- spoiled ballots: decryptBallot (RunRemoteDecryptor.java:264-269) ----
     def decrypt_ballots_record(self, ballots, man) -> DecryptionRecord:

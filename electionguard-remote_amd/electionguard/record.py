@@ -17,7 +17,11 @@ path produces.  Every exponentiation runs on the GPU through the C ABI:
                          (decryptBallot, RunRemoteDecryptor.java:264-269);
   * ``ballot_codes``     when the record carries confirmation codes: the device ballot hashes of
                          ``ballots`` chain to ``codes`` from ``code_seed`` (ballot chaining;
-                         electionguard.codes, include/eg_hip_codes.h).
+                         electionguard.codes, include/eg_hip_codes.h);
+  * ``contest_data``     when the caller passes the ballots' sealed contest data: on public data
+                         alone, one ciphertext per (ballot, contest), every c0 in [1, p) with
+                         c0^q = 1, every c1 as long as the recorded numBytes
+                         (electionguard.contest_data, include/eg_hip_contestdata.h).
 
 Manifest and protobuf-format checks are record plumbing outside the hot path and
 are not restated; the ballot hash chain is checked when the record carries it.
@@ -30,6 +34,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 
 from . import codes as _codes
+from . import contest_data as _cd
 from .ballot import AnyManifest, ElectionKey, EncryptedBallots, Manifest, Verifier  # noqa: F401
 from .codes import ManifestHashes
 from .core.group import GroupContext, as_p_array
@@ -78,9 +83,11 @@ def _codes_ok(group: GroupContext, rec: ElectionRecord) -> bool:
     return ok.shape == (nb,) and bool(ok.all())
 
 
-def verify_election_record(group: GroupContext, rec: ElectionRecord, window_bits: int = 8) -> Dict[str, bool]:
+def verify_election_record(group: GroupContext, rec: ElectionRecord, window_bits: int = 8,
+                           contest_data: Optional["_cd.SealedContestData"] = None) -> Dict[str, bool]:
     """-> {check name: passed}.  A check that cannot run because an earlier one failed
-    structurally (wrong shapes) reports False."""
+    structurally (wrong shapes) reports False.  contest_data: the ballots' sealed contest data,
+    checked when given (nothing changes without it)."""
     out: Dict[str, bool] = {}
     comm = [k for g in rec.guardians for k in g.commitments]
     prf = [p for g in rec.guardians for p in g.proofs]
@@ -105,6 +112,8 @@ def verify_election_record(group: GroupContext, rec: ElectionRecord, window_bits
     out["ballots"] = bool(ok_s.all() and ok_c.all()) and cast_ok
     if rec.codes is not None:
         out["ballot_codes"] = _codes_ok(group, rec)
+    if contest_data is not None:
+        out["contest_data"] = _cd.verify_public(group, man, nb, contest_data)
     et = np.ascontiguousarray(rec.encrypted_tally, dtype=np.uint8).reshape(-1, 2, 512)
     out["tally"] = et.shape == tally.shape and bool(np.array_equal(et, tally))
     dtexts = np.ascontiguousarray(rec.decryption.texts, dtype=np.uint8).reshape(-1, 2, 512)
