@@ -1,0 +1,278 @@
+// eg_capi_range.inc — 0..L range proofs of ciphertexts (include/eg_hip_range.h; included by
+// eg_capi.hip after eg_capi_contestdata.inc: the key, table, job-cache and launch helpers are
+// eg_capi_ballot.inc's, aligned16 is eg_capi_codes.inc's).  Kernels: eg_range.hpp and k_pow.
+//
+// Verifier jobs per item (B = L + 1 branches).  Branches 0 and 1 are the selection verifier's
+// pair jobs, one per base: the alpha job is its SA shape (a_0, a_1; comb shared by e_0, e_1), the
+// beta job its SB shape (b_0, b_1 with the g term -e_1), both with the residue pair (resid = 1)
+// and both keeping their comb powers y_k = base^(2^(52 k)) (yout).  Every further branch j >= 2 is
+// one single-output comb job per base that takes those powers back (gather = 1: four loads instead
+// of 208 squarings) and builds only its 32-entry subset table.  A gather job's record holds the
+// source job in J[2], where a pair job holds its second exponent, so gather jobs carry one
+// exponent each; DESIGN.md §13 has the multiply counts of this choice against rebuilt pairs.
+
+static_assert(EG_RANGE_MAX_LIMIT == 15, "eg_hip_range.h and the chunk sizing disagree");
+
+// Items per chunk: a chunk holds at most kRangeChunkJobs verifier jobs (2 L per item), so the
+// k_pow scratch and the commitment space shrink per item as L grows (32,768 items at L = 1, 2,184
+// at L = 15).  The prover (L + 2 jobs per item) uses the same item count.
+static constexpr size_t kRangeChunkJobs = (size_t)1 << 16;
+static size_t range_chunk(uint32_t L) { return std::max<size_t>(1, kRangeChunkJobs / (2 * (size_t)L)); }
+
+static int range_args(eg_ctx* c, const uint8_t* K_be, const uint8_t* qbar_be, size_t n, uint32_t L, bool data_ok) {
+  if (!c || !K_be || !qbar_be || (n && !data_ok)) return fail(EG_ERR_ARG, "range: null argument");
+  if (L < 1 || L > EG_RANGE_MAX_LIMIT) return fail(EG_ERR_ARG, "range: limit outside [1, 15]");
+  return EG_OK;
+}
+
+static inline unsigned rgrid(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
+
+// ---------------------------------------------------------------------------------
+// verify
+// ---------------------------------------------------------------------------------
+// One chunk of n <= range_chunk(L) items, device pointers, enqueued on the ctx stream (d_qbar and
+// the key are set by the caller, who holds the lock).
+static int range_verify_chunk_locked(eg_ctx* c, size_t n, uint32_t L, const uint8_t* d_cts, const uint8_t* d_proofs,
+                                     uint8_t* d_ok) {
+  const FbTab G = c->gtab->tab(), K = c->Ktab->tab();
+  const size_t B = (size_t)L + 1, nx = n * (B - 2);  // nx: jobs of the branches past the first pair, per base
+  int rc;
+  uint32_t *E = nullptr, *COMM = nullptr, *YA = nullptr, *YB = nullptr, *RZ = nullptr;
+  uint8_t *LTP = nullptr, *SC = nullptr, *OKS = nullptr, *COMM_BE = nullptr;
+  // scalars: [proof rows n*2B (c_j, v_j)][g terms n*B (-j e_j)]
+  const size_t off_g = n * 2 * B;
+  if ((rc = ws_get(c, W_E0, n * 2 * kW * 4, (void**)&E))) return rc;
+  if ((rc = ws_get(c, W_E1, n * 2 * B * kW * 4, (void**)&COMM))) return rc;
+  if ((rc = ws_get(c, W_FLAGS, n * 2, (void**)&LTP))) return rc;
+  if ((rc = ws_get(c, W_SCAL, (off_g + n * B) * 32, (void**)&SC))) return rc;
+  if ((rc = ws_get(c, W_OK0, n, (void**)&OKS))) return rc;
+  if ((rc = ws_get(c, W_BE0, n * 2 * B * 512, (void**)&COMM_BE))) return rc;
+  if ((rc = ws_get(c, W_YA, n * (kCombH - 1) * kW * 4, (void**)&YA))) return rc;
+  if ((rc = ws_get(c, W_YB, n * (kCombH - 1) * kW * 4, (void**)&YB))) return rc;
+  if ((rc = ws_get(c, W_RZ, n * 4 * kW * 4, (void**)&RZ))) return rc;
+  // 1. import the ciphertexts (range flags alpha, beta < p)
+  if ((rc = launch_import(c, d_cts, n * 2, E, LTP))) return rc;
+  // 2. scalars: a working copy of the proofs (negated in place under EG_RESPONSE_PLUS), the g terms
+  HIPCHK(hipMemcpyAsync(SC, d_proofs, n * B * 64, hipMemcpyDeviceToDevice, c->stream));
+  hipLaunchKernelGGL(k_range_scalars, dim3(rgrid(n)), dim3(kBlock), 0, c->stream, c->d_q, SC, (uint64_t)n, L,
+                     SC + off_g * 32, OKS, c->resp_plus);
+  HIPCHK(hipGetLastError());
+  // 3. commitments
+  const std::string key = "rv/" + std::to_string(n) + "/" + std::to_string(L);
+  std::vector<const uint32_t*> jv;
+  rc = cached_job_set(c, key, {"A", "B", "XA", "XB"}, [&]() {
+    auto A = new_jobs(n), Bj = new_jobs(n), XA = new_jobs(nx), XB = new_jobs(nx);
+    for (size_t i = 0; i < n; ++i) {
+      const uint32_t s0 = (uint32_t)(i * 2 * B), o0 = (uint32_t)(i * 2 * B);  // scalar / commitment row of item i
+      uint32_t* a = &A[i * kJobWords];
+      uint32_t* b = &Bj[i * kJobWords];
+      a[0] = (uint32_t)(i * 2); a[1] = s0; a[2] = s0 + 2; a[3] = o0; a[4] = o0 + 2; a[5] = s0 + 1; a[7] = s0 + 3;
+      b[0] = (uint32_t)(i * 2 + 1); b[1] = s0; b[2] = s0 + 2; b[3] = o0 + 1; b[4] = o0 + 3; b[5] = s0 + 1;
+      b[7] = s0 + 3; b[8] = (uint32_t)(off_g + i * B + 1);
+      for (size_t j = 2; j < B; ++j) {
+        uint32_t* xa = &XA[(i * (B - 2) + (j - 2)) * kJobWords];
+        uint32_t* xb = &XB[(i * (B - 2) + (j - 2)) * kJobWords];
+        const uint32_t cj = s0 + (uint32_t)(2 * j), vj = cj + 1;
+        xa[0] = (uint32_t)(i * 2); xa[1] = cj; xa[2] = (uint32_t)i; xa[3] = o0 + (uint32_t)(2 * j); xa[5] = vj;
+        xb[0] = (uint32_t)(i * 2 + 1); xb[1] = cj; xb[2] = (uint32_t)i; xb[3] = o0 + (uint32_t)(2 * j + 1); xb[5] = vj;
+        xb[6] = (uint32_t)(off_g + i * B + j);
+      }
+    }
+    return std::vector<std::vector<uint32_t>>{std::move(A), std::move(Bj), std::move(XA), std::move(XB)};
+  }, jv);
+  if (rc) return rc;
+  const bool gat = c->use_comb != 0;
+  PowShape SA{};  // a_0 = alpha^e0 g^v0, a_1 = alpha^e1 g^v1 (the selection verifier's alpha shape)
+  SA.has_base = 1; SA.nout = 2; SA.nfb[0] = 1; SA.nfb[1] = 1; SA.exp_bytes = 32; SA.comb = 1; SA.resid = 1;
+  SA.rows = c->sel_rows; SA.blocks = c->sel_blocks;
+  PowShape SB = SA;  // b_0 = beta^e0 K^v0, b_1 = beta^e1 K^v1 g^-e1
+  SB.nfb[1] = 2; SB.tab[0][0] = 1; SB.tab[1][0] = 1; SB.tab[1][1] = 0;
+  PowShape XA{};  // a_j = alpha^ej g^vj on the pair job's comb powers
+  XA.has_base = 1; XA.nout = 1; XA.nfb[0] = 1; XA.exp_bytes = 32; XA.comb = gat ? 1u : 0u; XA.gather = gat ? 1u : 0u;
+  PowShape XB = XA;  // b_j = beta^ej K^vj g^(-j ej)
+  XB.nfb[0] = 2; XB.tab[0][0] = 1; XB.tab[0][1] = 0;
+  {
+    PowTail T{};  // the beta pair jobs ride in the alpha launch's last sub-launch
+    T.S = SB; T.jobs = jv[1]; T.njobs = n; T.yout = gat ? YB : nullptr; T.rout = RZ + n * 2 * kW;
+    if ((rc = launch_pow(c, SA, jv[0], n, E, SC, COMM, G, K, gat ? YA : nullptr, nullptr, &T, RZ))) return rc;
+  }
+  if (nx) {
+    PowTail T{};
+    T.S = XB; T.jobs = jv[3]; T.njobs = nx; T.ygat = YB;
+    if ((rc = launch_pow(c, XA, jv[2], nx, E, SC, COMM, G, K, nullptr, YA, &T))) return rc;
+  }
+  // alpha^q == 1 and beta^q == 1 fold into the range flags
+  LAUNCH_F(c, k_resid_check, dim3(grid_for(n)), c->d, RZ, (uint32_t)n, LTP, 2u);
+  LAUNCH_F(c, k_resid_check, dim3(grid_for(n)), c->d, RZ + n * 2 * kW, (uint32_t)n, LTP + 1, 2u);
+  HIPCHK(hipGetLastError());
+  // 4. canonical bytes of the commitments, 5. the Fiat-Shamir check on the caller's proof rows
+  if ((rc = launch_export(c, COMM, n * 2 * B, COMM_BE))) return rc;
+  hipLaunchKernelGGL(k_range_hash, dim3(rgrid(n)), dim3(kBlock), 0, c->stream, c->d_q, c->d_qbar, (uint64_t)n, L, d_cts,
+                     COMM_BE, c->keys.front().d_K, c->pre_order, d_proofs, OKS, LTP, d_ok, (uint8_t*)nullptr,
+                     c->hash_fmt);
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+
+extern "C" int eg_range_verify_dev(eg_ctx* c, const uint8_t K_be[512], const uint8_t qbar_be[32], size_t n, uint32_t L,
+                                   const uint8_t* d_cts, const uint8_t* d_proofs, uint8_t* d_ok) {
+  int rc;
+  if ((rc = range_args(c, K_be, qbar_be, n, L, d_cts && d_proofs && d_ok))) return rc;
+  if (!aligned16({d_cts, d_proofs})) return fail(EG_ERR_ARG, "range: device pointer not 16-byte aligned");
+  if (!n) return EG_OK;
+  Locked lk(c);
+  if ((rc = use_key_locked(c, K_be))) return rc;
+  HIPCHK(hipMemcpyAsync(c->d_qbar, qbar_be, 32, hipMemcpyHostToDevice, c->stream));
+  const size_t chunk = range_chunk(L), B = (size_t)L + 1;
+  for (size_t i0 = 0; i0 < n; i0 += chunk) {
+    const size_t m = std::min(chunk, n - i0);
+    if ((rc = range_verify_chunk_locked(c, m, L, d_cts + i0 * 1024, d_proofs + i0 * B * 64, d_ok + i0))) return rc;
+  }
+  return EG_OK;
+}
+
+extern "C" int eg_range_verify(eg_ctx* c, const uint8_t K_be[512], const uint8_t qbar_be[32], size_t n, uint32_t L,
+                               const uint8_t* cts, const uint8_t* proofs, uint8_t* ok) {
+  int rc;
+  if ((rc = range_args(c, K_be, qbar_be, n, L, cts && proofs && ok))) return rc;
+  if (!n) return EG_OK;
+  Locked lk(c);
+  if ((rc = use_key_locked(c, K_be))) return rc;
+  HIPCHK(hipMemcpyAsync(c->d_qbar, qbar_be, 32, hipMemcpyHostToDevice, c->stream));
+  const size_t chunk = range_chunk(L), B = (size_t)L + 1, first = std::min(chunk, n);
+  uint8_t *d_cts = nullptr, *d_pr = nullptr, *d_ok = nullptr;
+  if ((rc = ws_get(c, W_H0, first * 1024, (void**)&d_cts))) return rc;
+  if ((rc = ws_get(c, W_H1, first * B * 64, (void**)&d_pr))) return rc;
+  if ((rc = ws_get(c, W_H2, first, (void**)&d_ok))) return rc;
+  // staged chunk by chunk: the device holds one chunk however many items come in
+  for (size_t i0 = 0; i0 < n; i0 += chunk) {
+    const size_t m = std::min(chunk, n - i0);
+    HIPCHK(hipMemcpyAsync(d_cts, cts + i0 * 1024, m * 1024, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_pr, proofs + i0 * B * 64, m * B * 64, hipMemcpyHostToDevice, c->stream));
+    if ((rc = range_verify_chunk_locked(c, m, L, d_cts, d_pr, d_ok))) return rc;
+    HIPCHK(hipMemcpyAsync(ok + i0, d_ok, m, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  return EG_OK;
+}
+
+// ---------------------------------------------------------------------------------
+// prove
+// ---------------------------------------------------------------------------------
+// One chunk of n <= range_chunk(L) items, device pointers.  Fixed-base only, like
+// encrypt_chunk_locked: per item B simulated pairs (a_j, b_j) = (g^s_j, K^s_j g^t_j) into the
+// item's commitment row and the real pair (g^u, K^u) apart, whatever the value; k_range_order
+// then puts the real pair at branch m with masks.  The job tables do not depend on the values.
+static int range_prove_chunk_locked(eg_ctx* c, size_t n, uint32_t L, const uint8_t* d_cts, const uint8_t* d_values,
+                                    const uint8_t* d_R, const uint8_t* d_nonces, uint8_t* d_proofs) {
+  int rc;
+  FbTab G{}, K{};
+  if ((rc = enc_tables_locked(c, &G, &K))) return rc;
+  const bool ct = c->ct_encrypt != 0;
+  const size_t B = (size_t)L + 1, nw = 2 * B + 1;
+  // scalars: [nonces n*nw (u, c_0, v_0, ...)][s n*B][t n*B]
+  const size_t off_s = n * nw, off_t = off_s + n * B;
+  // elements: [commitments n*2B][real pairs n*2]
+  const size_t oRE = n * 2 * B, nU = oRE + n * 2;
+  uint8_t *SC = nullptr, *CH = nullptr, *COMM_BE = nullptr;
+  uint32_t* U = nullptr;
+  if ((rc = ws_get(c, W_SCAL, (off_t + n * B) * 32, (void**)&SC))) return rc;
+  if ((rc = ws_get(c, W_E0, nU * kW * 4, (void**)&U))) return rc;
+  if ((rc = ws_get(c, W_BE0, oRE * 512, (void**)&COMM_BE))) return rc;
+  if ((rc = ws_get(c, W_OK0, n * 32, (void**)&CH))) return rc;
+  HIPCHK(hipMemcpyAsync(SC, d_nonces, n * nw * 32, hipMemcpyDeviceToDevice, c->stream));
+  hipLaunchKernelGGL(k_range_prep, dim3(rgrid(n)), dim3(kBlock), 0, c->stream, c->d_q, d_values, SC, d_R, (uint64_t)n,
+                     L, SC + off_s * 32, SC + off_t * 32, c->resp_plus);
+  HIPCHK(hipGetLastError());
+  const std::string key = "rp/" + std::to_string(n) + "/" + std::to_string(L);
+  std::vector<const uint32_t*> jv;
+  rc = cached_job_set(c, key, {"S", "R"}, [&]() {
+    auto S = new_jobs(n * B), Rj = new_jobs(n);
+    for (size_t i = 0; i < n; ++i) {
+      for (size_t j = 0; j < B; ++j) {
+        uint32_t* s = &S[(i * B + j) * kJobWords];  // a_j = g^s_j ; b_j = K^s_j g^t_j
+        const uint32_t sj = (uint32_t)(off_s + i * B + j);
+        s[3] = (uint32_t)(i * 2 * B + 2 * j); s[4] = s[3] + 1; s[5] = sj; s[7] = sj;
+        s[8] = (uint32_t)(off_t + i * B + j);
+      }
+      uint32_t* r = &Rj[i * kJobWords];  // g^u ; K^u
+      r[3] = (uint32_t)(oRE + i * 2); r[4] = r[3] + 1; r[5] = (uint32_t)(i * nw); r[7] = r[5];
+    }
+    return std::vector<std::vector<uint32_t>>{std::move(S), std::move(Rj)};
+  }, jv);
+  if (rc) return rc;
+  {
+    PowShape S{};
+    S.nout = 2; S.nfb[0] = 1; S.nfb[1] = 2; S.exp_bytes = 32; S.tab[1][0] = 1; S.tab[1][1] = 0;
+    PowTail T{};  // the real pairs fill the simulated pairs' last round
+    T.S.nout = 2; T.S.nfb[0] = 1; T.S.nfb[1] = 1; T.S.exp_bytes = 32; T.S.tab[1][0] = 1;
+    T.jobs = jv[1]; T.njobs = n;
+    if ((rc = launch_pow(c, S, jv[0], n * B, U, SC, U, G, K, nullptr, nullptr, &T, nullptr, ct))) return rc;
+  }
+  constexpr size_t kQuads = 2 * kW / 4;
+  hipLaunchKernelGGL(k_range_order, dim3(rgrid(n * kQuads)), dim3(kBlock), 0, c->stream, U, U + oRE * kW, d_values,
+                     (uint64_t)n, L);
+  HIPCHK(hipGetLastError());
+  if ((rc = launch_export(c, U, oRE, COMM_BE))) return rc;
+  hipLaunchKernelGGL(k_range_hash, dim3(rgrid(n)), dim3(kBlock), 0, c->stream, c->d_q, c->d_qbar, (uint64_t)n, L, d_cts,
+                     COMM_BE, c->keys.front().d_K, c->pre_order, (const uint8_t*)nullptr, (const uint8_t*)nullptr,
+                     (const uint8_t*)nullptr, (uint8_t*)nullptr, CH, c->hash_fmt);
+  hipLaunchKernelGGL(k_range_finish, dim3(rgrid(n)), dim3(kBlock), 0, c->stream, c->d_q, d_values, SC, d_R, CH,
+                     (uint64_t)n, L, d_proofs, c->resp_plus);
+  HIPCHK(hipGetLastError());
+  return EG_OK;
+}
+
+extern "C" int eg_range_prove_dev(eg_ctx* c, const uint8_t K_be[512], const uint8_t qbar_be[32], size_t n, uint32_t L,
+                                  const uint8_t* d_cts, const uint8_t* d_values, const uint8_t* d_R,
+                                  const uint8_t* d_nonces, uint8_t* d_proofs) {
+  int rc;
+  if ((rc = range_args(c, K_be, qbar_be, n, L, d_cts && d_values && d_R && d_nonces && d_proofs))) return rc;
+  if (!aligned16({d_cts, d_R, d_nonces, d_proofs}))
+    return fail(EG_ERR_ARG, "range: device pointer not 16-byte aligned");
+  if (!n) return EG_OK;
+  Locked lk(c);
+  if ((rc = use_key_locked(c, K_be))) return rc;
+  HIPCHK(hipMemcpyAsync(c->d_qbar, qbar_be, 32, hipMemcpyHostToDevice, c->stream));
+  const size_t chunk = range_chunk(L), B = (size_t)L + 1;
+  for (size_t i0 = 0; i0 < n; i0 += chunk) {
+    const size_t m = std::min(chunk, n - i0);
+    if ((rc = range_prove_chunk_locked(c, m, L, d_cts + i0 * 1024, d_values + i0, d_R + i0 * 32,
+                                       d_nonces + i0 * (2 * B + 1) * 32, d_proofs + i0 * B * 64)))
+      return rc;
+  }
+  return EG_OK;
+}
+
+extern "C" int eg_range_prove(eg_ctx* c, const uint8_t K_be[512], const uint8_t qbar_be[32], size_t n, uint32_t L,
+                              const uint8_t* cts, const uint8_t* values, const uint8_t* R, const uint8_t* nonces,
+                              uint8_t* proofs) {
+  int rc;
+  if ((rc = range_args(c, K_be, qbar_be, n, L, cts && values && R && nonces && proofs))) return rc;
+  for (size_t i = 0; i < n; ++i)
+    if (values[i] > L)
+      return fail(EG_ERR_ARG, "range: values[" + std::to_string(i) + "] = " + std::to_string((unsigned)values[i]) +
+                                  " exceeds the limit " + std::to_string(L));
+  if (!n) return EG_OK;
+  Locked lk(c);
+  if ((rc = use_key_locked(c, K_be))) return rc;
+  HIPCHK(hipMemcpyAsync(c->d_qbar, qbar_be, 32, hipMemcpyHostToDevice, c->stream));
+  const size_t chunk = range_chunk(L), B = (size_t)L + 1, nw = 2 * B + 1, first = std::min(chunk, n);
+  uint8_t *d_cts = nullptr, *d_val = nullptr, *d_R = nullptr, *d_non = nullptr, *d_pr = nullptr;
+  if ((rc = ws_get(c, W_H0, first * 1024, (void**)&d_cts))) return rc;
+  if ((rc = ws_get(c, W_H1, first * B * 64, (void**)&d_pr))) return rc;
+  if ((rc = ws_get(c, W_H2, first, (void**)&d_val))) return rc;
+  if ((rc = ws_get(c, W_H3, first * 32, (void**)&d_R))) return rc;
+  if ((rc = ws_get(c, W_H4, first * nw * 32, (void**)&d_non))) return rc;
+  for (size_t i0 = 0; i0 < n; i0 += chunk) {
+    const size_t m = std::min(chunk, n - i0);
+    HIPCHK(hipMemcpyAsync(d_cts, cts + i0 * 1024, m * 1024, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_val, values + i0, m, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_R, R + i0 * 32, m * 32, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_non, nonces + i0 * nw * 32, m * nw * 32, hipMemcpyHostToDevice, c->stream));
+    if ((rc = range_prove_chunk_locked(c, m, L, d_cts, d_val, d_R, d_non, d_pr))) return rc;
+    HIPCHK(hipMemcpyAsync(proofs + i0 * B * 64, d_pr, m * B * 64, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  return EG_OK;
+}

@@ -56,6 +56,13 @@ EXPORTED_CONTEST_DATA = [
 ]
 
 
+# Every symbol declared in include/eg_hip_range.h (0..L range proofs of ciphertexts).
+EXPORTED_RANGE = [
+    "eg_range_prove", "eg_range_prove_dev",
+    "eg_range_verify", "eg_range_verify_dev",
+]
+
+
 class NativeUnavailable(RuntimeError):
     pass
 
@@ -151,6 +158,10 @@ def _sig(lib: ctypes.CDLL) -> None:
         "eg_seal_contest_data_dev": ([P, P, S, S, S, P, P, P, P, P, P], I),
         "eg_open_contest_data": ([P, S, S, S, P, P, P, P, P, P, P], I),
         "eg_open_contest_data_dev": ([P, S, S, S, P, P, P, P, P, P, P], I),
+        "eg_range_prove": ([P, P, P, S, U32, P, P, P, P, P], I),
+        "eg_range_prove_dev": ([P, P, P, S, U32, P, P, P, P, P], I),
+        "eg_range_verify": ([P, P, P, S, U32, P, P, P], I),
+        "eg_range_verify_dev": ([P, P, P, S, U32, P, P, P], I),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name)
