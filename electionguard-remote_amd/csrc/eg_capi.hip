@@ -33,10 +33,12 @@
 #include "../../include/eg_hip_codes.h"
 #include "../../include/eg_hip_contestdata.h"
 #include "../../include/eg_hip_range.h"
+#include "../../include/eg_hip_preencrypt.h"
 #include "eg_kernels.hpp"
 #include "eg_codes.hpp"
 #include "eg_hmac.hpp"
 #include "eg_range.hpp"
+#include "eg_preencrypt.hpp"
 #include "eg_pow16.h"
 
 using namespace eg;
@@ -1234,6 +1236,7 @@ extern "C" int eg_ctx_profile_end(eg_ctx* c, double* ms, double* mm, double* sqr
 #include "eg_capi_codes.inc"
 #include "eg_capi_contestdata.inc"
 #include "eg_capi_range.inc"
+#include "eg_capi_preencrypt.inc"
 #include "eg_capi_coalesce.inc"
 #include "eg_capi_comm.inc"
 

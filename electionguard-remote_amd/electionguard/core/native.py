@@ -63,6 +63,14 @@ EXPORTED_RANGE = [
 ]
 
 
+# Every symbol declared in include/eg_hip_preencrypt.h (pre-encrypted ballots).
+EXPORTED_PREENCRYPT = [
+    "eg_preencrypt_ballots", "eg_preencrypt_ballots_dev",
+    "eg_preencrypt_record", "eg_preencrypt_record_dev",
+    "eg_preencrypt_verify", "eg_preencrypt_verify_dev",
+]
+
+
 class NativeUnavailable(RuntimeError):
     pass
 
@@ -162,6 +170,12 @@ def _sig(lib: ctypes.CDLL) -> None:
         "eg_range_prove_dev": ([P, P, P, S, U32, P, P, P, P, P], I),
         "eg_range_verify": ([P, P, P, S, U32, P, P, P], I),
         "eg_range_verify_dev": ([P, P, P, S, U32, P, P, P], I),
+        "eg_preencrypt_ballots": ([P, P, S, S, P, U32] + [P] * 11, I),
+        "eg_preencrypt_ballots_dev": ([P, P, S, S, P, U32] + [P] * 11, I),
+        "eg_preencrypt_record": ([P, P, S, S, P, P, U32] + [P] * 10, I),
+        "eg_preencrypt_record_dev": ([P, P, S, S, P, P, U32] + [P] * 10, I),
+        "eg_preencrypt_verify": ([P, S, S, P, P, U32] + [P] * 11, I),
+        "eg_preencrypt_verify_dev": ([P, S, S, P, P, U32] + [P] * 11, I),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name)

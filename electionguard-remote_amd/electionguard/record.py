@@ -21,7 +21,12 @@ path produces.  Every exponentiation runs on the GPU through the C ABI:
   * ``contest_data``     when the caller passes the ballots' sealed contest data: on public data
                          alone, one ciphertext per (ballot, contest), every c0 in [1, p) with
                          c0^q = 1, every c1 as long as the recorded numBytes
-                         (electionguard.contest_data, include/eg_hip_contestdata.h).
+                         (electionguard.contest_data, include/eg_hip_contestdata.h);
+  * ``preencrypted``     when the caller passes the pre-encryption part of the record: every
+                         ballot passes the pre-encryption check against its published sorted lists
+                         and chosen vectors, and ``ballot_codes`` chains the confirmation hashes C
+                         where it otherwise chains the ballot hashes
+                         (electionguard.preencrypt, include/eg_hip_preencrypt.h).
 
 Manifest and protobuf-format checks are record plumbing outside the hot path and
 are not restated; the ballot hash chain is checked when the record carries it.
@@ -35,6 +40,7 @@ import numpy as np
 
 from . import codes as _codes
 from . import contest_data as _cd
+from . import preencrypt as _pre
 from .ballot import AnyManifest, ElectionKey, EncryptedBallots, Manifest, Verifier  # noqa: F401
 from .codes import ManifestHashes
 from .core.group import GroupContext, as_p_array
@@ -69,14 +75,29 @@ class ElectionRecord:
     hashes: Optional[ManifestHashes] = None             # the manifest's description hashes
 
 
-def _codes_ok(group: GroupContext, rec: ElectionRecord) -> bool:
+def _preencrypted_ok(group: GroupContext, rec: ElectionRecord, pre: "_pre.PreencryptedRecord") -> bool:
+    """Every contest of every ballot passes the pre-encryption check, and every recorded
+    confirmation hash is the one its sorted lists give."""
+    if rec.ballot_ids is None or rec.hashes is None:
+        return False
+    try:
+        okc, okb = _pre.verify_recorded(group, rec.manifest, rec.hashes, rec.ballot_ids, pre.sel_vecs, pre.sel_rank,
+                                        pre.sel_codes, pre.sorted, rec.ballots.cts, pre.conf, pre.code_bytes)
+    except ValueError:  # wrong shapes
+        return False
+    return okb.shape == (rec.ballots.n,) and bool(okc.all() and okb.all())
+
+
+def _codes_ok(group: GroupContext, rec: ElectionRecord, conf: Optional[np.ndarray] = None) -> bool:
     """The ballots' hashes, taken on the device, chain to the recorded codes (every ballot, cast
-    or spoiled: a spoiled ballot keeps its place in the chain)."""
+    or spoiled: a spoiled ballot keeps its place in the chain).  conf: pre-encrypted ballots'
+    confirmation hashes, which enter the chain in the ballot hashes' place."""
     nb = rec.ballots.n
     if any(x is None for x in (rec.ballot_ids, rec.timestamps, rec.code_seed, rec.hashes)):
         return False
     try:
-        B = _codes.ballot_hashes(group, rec.manifest, rec.hashes, rec.ballot_ids, rec.ballots.cts)
+        B = conf if conf is not None else \
+            _codes.ballot_hashes(group, rec.manifest, rec.hashes, rec.ballot_ids, rec.ballots.cts)
         ok = _codes.verify_code_chain(group, rec.code_seed, rec.timestamps, B, rec.codes)
     except ValueError:  # wrong shapes
         return False
@@ -84,10 +105,13 @@ def _codes_ok(group: GroupContext, rec: ElectionRecord) -> bool:
 
 
 def verify_election_record(group: GroupContext, rec: ElectionRecord, window_bits: int = 8,
-                           contest_data: Optional["_cd.SealedContestData"] = None) -> Dict[str, bool]:
+                           contest_data: Optional["_cd.SealedContestData"] = None,
+                           preencrypted: Optional["_pre.PreencryptedRecord"] = None) -> Dict[str, bool]:
     """-> {check name: passed}.  A check that cannot run because an earlier one failed
     structurally (wrong shapes) reports False.  contest_data: the ballots' sealed contest data,
-    checked when given (nothing changes without it)."""
+    checked when given (nothing changes without it).  preencrypted: the pre-encryption part of a
+    record of pre-encrypted ballots, checked when given; the code chain then runs over its
+    confirmation hashes."""
     out: Dict[str, bool] = {}
     comm = [k for g in rec.guardians for k in g.commitments]
     prf = [p for g in rec.guardians for p in g.proofs]
@@ -111,7 +135,9 @@ def verify_election_record(group: GroupContext, rec: ElectionRecord, window_bits
     ok_s, ok_c, tally = Verifier(group, key, rec.qbar, man).verify(rec.ballots, cast=cast)
     out["ballots"] = bool(ok_s.all() and ok_c.all()) and cast_ok
     if rec.codes is not None:
-        out["ballot_codes"] = _codes_ok(group, rec)
+        out["ballot_codes"] = _codes_ok(group, rec, None if preencrypted is None else preencrypted.conf)
+    if preencrypted is not None:
+        out["preencrypted"] = _preencrypted_ok(group, rec, preencrypted)
     if contest_data is not None:
         out["contest_data"] = _cd.verify_public(group, man, nb, contest_data)
     et = np.ascontiguousarray(rec.encrypted_tally, dtype=np.uint8).reshape(-1, 2, 512)
