@@ -604,11 +604,13 @@ static int launch_pow(eg_ctx* c, const PowShape& S, const uint32_t* d_jobs, size
   return EG_OK;
 }
 
-// Product reduction of `groups` groups of `len` device elements (group layout gm,
-// element stride `stride`); result -> d_out[g].  Fully asynchronous.
-// mask (optional, len bytes): element k takes part only if mask[k] != 0 (first pass only).
-static int run_prod(eg_ctx* c, const uint32_t* d_in, GroupMap gm, size_t groups, size_t len, size_t stride,
-                    uint32_t* d_out, const uint8_t* mask = nullptr) {
+// The product tree of run_prod / run_prod_tab: `groups` products of `len` elements each, pass by
+// pass.  pass(src, len, stride, ch, nchunk, dst, last) launches one pass that multiplies every
+// group's `len` elements in nchunk runs of ch; src == nullptr is the first pass (the caller's
+// input, layout and mask), later passes read the previous one's partial products, group g's
+// contiguous at src + g * len.  Fully asynchronous.
+template <class Pass>
+static int prod_tree(eg_ctx* c, size_t groups, size_t len, size_t stride, uint32_t* d_out, Pass pass) {
   if (!groups) return EG_OK;
   if (len == 0) return fail(EG_ERR_ARG, "empty product");
   // Short products (contest aggregates, residue pairs: len = spc) run in one pass.  Long ones
@@ -622,26 +624,49 @@ static int run_prod(eg_ctx* c, const uint32_t* d_in, GroupMap gm, size_t groups,
   if (rc) return rc;
   uint32_t* ping[2] = {tmp, tmp + maxpart * kW};
   size_t cur_len = len, cur_stride = stride;
-  const uint32_t* src = d_in;
+  const uint32_t* src = nullptr;
   int pi = 0;
   while (true) {
     const uint32_t nchunk = (uint32_t)((cur_len + chunk - 1) / chunk);
-    const uint32_t ch = nchunk == 1 ? (uint32_t)cur_len : chunk;
-    uint32_t* dst = (nchunk == 1) ? d_out : ping[pi];
-    const size_t njobs = groups * nchunk;
-    LAUNCH_F(c, k_prod, dim3(grid_for(njobs)), c->d, src, gm, (uint32_t)groups,
-                       (uint32_t)cur_len, (uint32_t)cur_stride, ch, nchunk, dst, mask);
+    const bool last = nchunk == 1;
+    uint32_t* dst = last ? d_out : ping[pi];
+    pass(src, (uint32_t)cur_len, (uint32_t)cur_stride, last ? (uint32_t)cur_len : chunk, nchunk, dst, last);
     HIPCHK(hipGetLastError());
-    if (nchunk == 1) break;
-    mask = nullptr;  // later passes multiply partial products
-    // next round: group g's partials are contiguous at g*nchunk
-    gm = GroupMap{1, 1, 0, 0, nchunk};
+    if (last) break;
     src = dst;
     cur_len = nchunk;
     cur_stride = 1;
     pi ^= 1;
   }
   return EG_OK;
+}
+
+// Product reduction of `groups` groups of `len` device elements (group layout gm,
+// element stride `stride`); result -> d_out[g].
+// mask (optional, len bytes): element k takes part only if mask[k] != 0 (first pass only).
+static int run_prod(eg_ctx* c, const uint32_t* d_in, GroupMap gm, size_t groups, size_t len, size_t stride,
+                    uint32_t* d_out, const uint8_t* mask = nullptr) {
+  return prod_tree(c, groups, len, stride, d_out,
+                   [&](const uint32_t* src, uint32_t n, uint32_t st, uint32_t ch, uint32_t nchunk, uint32_t* dst, bool) {
+                     LAUNCH_F(c, k_prod, dim3(grid_for(groups * nchunk)), c->d, src ? src : d_in,
+                              src ? GroupMap{1, 1, 0, 0, n} : gm, (uint32_t)groups, n, st, ch, nchunk, dst,
+                              src ? nullptr : mask);
+                   });
+}
+
+// run_prod with table-addressed groups (k_prod_tab): group g starts at element
+// tab[g % period] + (g / period) * period_stride and its product goes to element
+// otab[g % period] + (g / period) * ostride of d_out (otab == nullptr: element g).
+static int run_prod_tab(eg_ctx* c, const uint32_t* d_in, const uint32_t* tab, size_t period, size_t period_stride,
+                        size_t groups, size_t len, size_t stride, uint32_t* d_out, const uint32_t* otab,
+                        size_t ostride, const uint8_t* mask = nullptr) {
+  return prod_tree(c, groups, len, stride, d_out,
+                   [&](const uint32_t* src, uint32_t n, uint32_t st, uint32_t ch, uint32_t nchunk, uint32_t* dst, bool last) {
+                     LAUNCH_F(c, k_prod_tab, dim3(grid_for(groups * nchunk)), c->d, src ? src : d_in,
+                              src ? nullptr : tab, (uint32_t)period, src ? n : (uint32_t)period_stride,
+                              (uint32_t)groups, n, st, ch, nchunk, dst, last ? otab : nullptr, (uint32_t)ostride,
+                              src ? nullptr : mask);
+                   });
 }
 
 // ---- fixed-base table build ----

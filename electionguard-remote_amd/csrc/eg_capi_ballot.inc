@@ -7,6 +7,14 @@
 //   eg_trustee_decrypt_batch DecryptingTrustee.directDecrypt / compensatedDecrypt
 //                            (RunRemoteDecryptingTrustee.java:189-193, 227-232)
 //   eg_verify_shares         share-proof check inside Decryption.decrypt (RunRemoteDecryptor.java:261-262)
+//
+// Verification and encryption have one chunk path for every ballot shape: verify_chunk_locked,
+// encrypt_chunk_locked and the four drivers around them (host / device pointers) take a ManShape.
+// The selection part of a chunk works on ns = nbc * nsel jobs and does not know the contests.
+// The contest layer (aggregates, contest scalars, contest flags, nonce sums, tally) and the
+// k_pow launch plan are the only places that tell a uniform shape (the entry points here:
+// arithmetic addressing, the benchmark's kernels and plan) from a table-addressed one (the
+// entry points of eg_capi_manifest.inc: per-contest device tables).
 
 static inline unsigned tgrid(size_t n) { return (unsigned)((n + 255) / 256); }
 
@@ -204,11 +212,8 @@ extern "C" int eg_set_election_key(eg_ctx* c, const uint8_t K_be[512], int wbits
 }
 
 // ---------------------------------------------------------------------------------
-// verification + tally
+// the ballot shape and the contest layer
 // ---------------------------------------------------------------------------------
-// One chunk of <= kVerifyChunk ballots: every proof of ballots [0, nbc) of the given device
-// arrays, and (tally != nullptr) their per-selection products, written to tally (first
-// chunk) or multiplied into it.  d_qbar and the key tables are set by the caller.
 static constexpr size_t kVerifyChunk = 16384;
 // Very wide manifests get fewer ballots per chunk, so one chunk never holds more than
 // kChunkSelections selection jobs (~14 KB of device working set each, plus the k_pow
@@ -234,214 +239,461 @@ static bool manifest_ok(size_t nc, size_t spc) {
   return nc && spc && nc <= kMaxSelections && spc <= kMaxSelections && nc * spc <= kMaxSelections;
 }
 
-// cast (optional, nbc bytes on the device): only ballots with cast[b] != 0 enter the tally; the
-// others (spoiled ballots, RunRemoteDecryptor.java:264-269) are verified but not tallied.
-static int verify_chunk_locked(eg_ctx* c, size_t nbc, size_t nc, size_t spc, size_t ph, uint32_t limit,
-                               const uint8_t* cts, const uint8_t* d_rproof, const uint8_t* d_cproof,
-                               const uint8_t* d_cast, uint8_t* d_ok_sel, uint8_t* d_ok_con, uint32_t* tally,
-                               bool first) {
-  const FbTab G = c->gtab->tab(), K = c->Ktab->tab();
-  const size_t nsel = nc * spc, nrs = spc - ph, nreal = nc * nrs;
-  int rc;
-  {
-    const size_t ns = nbc * nsel, ncn = nbc * nc;
-    uint32_t *E = nullptr, *COMM = nullptr;
-    uint8_t *LTP = nullptr, *SC = nullptr, *OKR = nullptr, *OKC = nullptr, *COMM_BE = nullptr, *CP_BE = nullptr;
-    if ((rc = ws_get(c, W_E0, (ns * 2 + ncn * 2) * kW * 4, (void**)&E))) return rc;
-    if ((rc = ws_get(c, W_E1, (ns * 4 + ncn * 2) * kW * 4, (void**)&COMM))) return rc;
-    if ((rc = ws_get(c, W_FLAGS, ns * 2, (void**)&LTP))) return rc;
-    const size_t off_c = ns * 4, off_neg = off_c + ncn * 2, off_negL = off_neg + ns;
-    if ((rc = ws_get(c, W_SCAL, (off_negL + ncn) * 32, (void**)&SC))) return rc;
-    if ((rc = ws_get(c, W_OK0, ns, (void**)&OKR))) return rc;
-    if ((rc = ws_get(c, W_OK1, ncn, (void**)&OKC))) return rc;
-    if ((rc = ws_get(c, W_BE0, (ns * 4 + ncn * 2) * 512, (void**)&COMM_BE))) return rc;
-    if ((rc = ws_get(c, W_BE1, ncn * 2 * 512, (void**)&CP_BE))) return rc;
-    // 1. import ciphertexts (range flags alpha, beta < p)
-    if ((rc = launch_import(c, cts, ns * 2, E, LTP))) return rc;
-    // 2. scalars: proofs + derived exponents (-c1, -L*c) + range flags
-    HIPCHK(hipMemcpyAsync(SC, d_rproof, ns * 128, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(SC + off_c * 32, d_cproof, ncn * 64, hipMemcpyDeviceToDevice, c->stream));
-    // plus convention: c0, c1 and c negated in place (the comb exponents), the g terms take +c1, +L c
-    hipLaunchKernelGGL(k_scalar_prep, dim3(tgrid(ns)), dim3(256), 0, c->stream, c->d_q, SC, (uint32_t)ns, 4u, 2u,
-                       1u, SC + off_neg * 32, OKR, c->resp_plus, 0x5u);
-    hipLaunchKernelGGL(k_scalar_prep, dim3(tgrid(ncn)), dim3(256), 0, c->stream, c->d_q, SC + off_c * 32,
-                       (uint32_t)ncn, 2u, 0u, limit, SC + off_negL * 32, OKC, c->resp_plus, 0x1u);
-    HIPCHK(hipGetLastError());
-    // 3. contest aggregates A = prod alpha, B = prod beta -> E[ns*2 + j*2 + {0,1}]
-    uint32_t* CP = E + ns * 2 * kW;
-    if ((rc = run_prod(c, E, GroupMap{2, (uint32_t)nc, 1, (uint32_t)(2 * spc), (uint32_t)(2 * nsel)}, ncn * 2, spc,
-                       2, CP)))
-      return rc;
-    // 4. commitments
-    const std::string key = "v/" + std::to_string(nbc) + "/" + std::to_string(nc) + "/" + std::to_string(spc);
-    std::vector<const uint32_t*> jv;
-    rc = cached_job_set(c, key, {"A", "B", "CA", "CB"}, [&]() {
-      auto A = new_jobs(ns), B = new_jobs(ns), CA = new_jobs(ncn), CB = new_jobs(ncn);
-      for (size_t i = 0; i < ns; ++i) {
-        uint32_t* a = &A[i * kJobWords];
-        uint32_t* b = &B[i * kJobWords];
-        const uint32_t c0 = (uint32_t)(i * 4), v0 = c0 + 1, c1 = c0 + 2, v1 = c0 + 3;
-        a[0] = (uint32_t)(i * 2); a[1] = c0; a[2] = c1; a[3] = (uint32_t)(i * 4 + 0); a[4] = (uint32_t)(i * 4 + 2);
-        a[5] = v0; a[7] = v1;
-        b[0] = (uint32_t)(i * 2 + 1); b[1] = c0; b[2] = c1; b[3] = (uint32_t)(i * 4 + 1); b[4] = (uint32_t)(i * 4 + 3);
-        b[5] = v0; b[7] = v1; b[8] = (uint32_t)(off_neg + i);
-      }
-      for (size_t j = 0; j < ncn; ++j) {
-        uint32_t* a = &CA[j * kJobWords];
-        uint32_t* b = &CB[j * kJobWords];
-        const uint32_t cc = (uint32_t)(off_c + j * 2), vv = cc + 1;
-        a[0] = (uint32_t)(ns * 2 + j * 2); a[1] = cc; a[3] = (uint32_t)(ns * 4 + j * 2); a[5] = vv;
-        b[0] = (uint32_t)(ns * 2 + j * 2 + 1); b[1] = cc; b[3] = (uint32_t)(ns * 4 + j * 2 + 1); b[5] = vv;
-        b[6] = (uint32_t)(off_negL + j);
-        a[2] = b[2] = (uint32_t)(j * spc);  // gather: the contest's first selection job (y_k source)
-      }
-      return std::vector<std::vector<uint32_t>>{std::move(A), std::move(B), std::move(CA), std::move(CB)};
-    }, jv);
+// The validated shape of one call (host side).  Contest k of a ballot owns spc[k] consecutive
+// selections from first[k], the placeholders last, and its constant proof uses limit[k].  The
+// contests are grouped into CLASSES of equal spc: PowShape.gather is part of k_pow's op
+// program, so a chunk has one contest job population per class.
+//   * table-addressed (man_shape, eg_capi_manifest.inc): the per-contest vectors are filled and
+//     go to the device as tables;
+//   * uniform (uniform_shape): nc contests of uspc selections, uph placeholders and limit ulimit,
+//     one class holding every contest.  No per-contest vector is filled (a 2^20-contest ballot
+//     must not build megabyte tables or a megabyte key per call); the contest layer below
+//     addresses such a shape by arithmetic.
+struct ManShape {
+  size_t nc = 0, nsel = 0, nreal = 0;
+  bool uniform = false;
+  uint32_t uspc = 0, uph = 0, ulimit = 0;         // the uniform shape's contest
+  std::vector<uint32_t> spc, first, limit, real;  // per contest; real: the real selections' indices
+  struct Class {
+    uint32_t spc;
+    size_t n;                       // contests in the class
+    std::vector<uint32_t> members;  // their indices, ascending (uniform: contest mi, not listed)
+    std::string tag;                // suffix of the class's table names in the cache
+  };
+  std::vector<Class> cls;  // ascending spc
+  std::string fam;         // prefix of the cache keys ("m": table-addressed)
+  std::string key;         // the spc list (verify: and the placeholders and limits), for the table cache
+  uint32_t member(const Class& C, size_t mi) const { return uniform ? (uint32_t)mi : C.members[mi]; }
+  uint32_t first_of(uint32_t k) const { return uniform ? k * uspc : first[k]; }
+};
+
+static ManShape uniform_shape(size_t nc, size_t spc, size_t ph, uint32_t limit) {
+  ManShape M;
+  M.uniform = true;
+  M.nc = nc;
+  M.nsel = nc * spc;
+  M.nreal = nc * (spc - ph);
+  M.uspc = (uint32_t)spc; M.uph = (uint32_t)ph; M.ulimit = limit;
+  M.cls.push_back(ManShape::Class{(uint32_t)spc, nc, {}, ""});
+  M.key = std::to_string(nc) + "/" + std::to_string(spc);
+  return M;
+}
+
+// The host tables of one cached set (cached_job_set) in upload order, each with the place its
+// device copy's address goes to.
+struct TableList {
+  std::vector<std::string> names;
+  std::vector<std::function<std::vector<uint32_t>()>> make;
+  std::vector<const uint32_t**> dst;
+  void add(const std::string& name, const uint32_t** d, std::function<std::vector<uint32_t>()> f) {
+    names.push_back(name); dst.push_back(d); make.push_back(std::move(f));
+  }
+};
+static int fetch_tables(eg_ctx* c, const std::string& key, const TableList& L) {
+  std::vector<const uint32_t*> dev;
+  const int rc = cached_job_set(c, key, L.names, [&]() {
+    std::vector<std::vector<uint32_t>> host;
+    for (const auto& f : L.make) host.push_back(f());
+    return host;
+  }, dev);
+  for (size_t i = 0; !rc && i < dev.size(); ++i) *L.dst[i] = dev[i];
+  return rc;
+}
+
+// The device tables the contest layer reads; a uniform shape has none (all stay null).
+struct ContestTabs {
+  const uint32_t *first = nullptr, *spc = nullptr, *limit = nullptr, *tally = nullptr;
+  std::vector<const uint32_t*> in, out;  // per class: the aggregate product's in / out tables
+  explicit ContestTabs(const ManShape& M) : in(M.cls.size(), nullptr), out(M.cls.size(), nullptr) {}
+};
+// Whether a set holds per-contest tables is decided here: the tables that lead a table-addressed
+// shape's set (verify: with the limits and the tally's table of real selections), and below
+// class ci's aggregate product tables (entry mi * 2 + comp of member contest k).
+static void add_contest_tables(TableList& L, const ManShape& M, ContestTabs& T, bool verify) {
+  if (M.uniform) return;
+  L.add("first", &T.first, [&M]() { return M.first; });
+  L.add("spc", &T.spc, [&M]() { return M.spc; });
+  if (!verify) return;
+  L.add("limit", &T.limit, [&M]() { return M.limit; });
+  L.add("tally", &T.tally, [&M]() {
+    std::vector<uint32_t> t;
+    for (uint32_t r : M.real)
+      for (uint32_t comp = 0; comp < 2; ++comp) t.push_back(r * 2 + comp);
+    return t;
+  });
+}
+static void add_class_tables(TableList& L, const ManShape& M, ContestTabs& T, size_t ci) {
+  if (M.uniform) return;
+  const ManShape::Class& C = M.cls[ci];
+  L.add("in" + C.tag, &T.in[ci], [&M, &C]() {
+    std::vector<uint32_t> t;
+    for (uint32_t k : C.members)
+      for (uint32_t comp = 0; comp < 2; ++comp) t.push_back(M.first[k] * 2 + comp);
+    return t;
+  });
+  L.add("out" + C.tag, &T.out[ci], [&C]() {
+    std::vector<uint32_t> t;
+    for (uint32_t k : C.members)
+      for (uint32_t comp = 0; comp < 2; ++comp) t.push_back(k * 2 + comp);
+    return t;
+  });
+}
+
+// The five steps that know the contests' sizes, each with an arithmetic arm (uniform shapes:
+// the kernels and arguments the uniform entry points have always used) and a table arm.
+// Aggregates A = prod alpha, B = prod beta of nbc ballots' contests: elems (ballot-major
+// ciphertext pairs) -> agg[(b nc + k) 2 + comp].  The table arm runs class by class, addressed
+// through the class's first selections and scattered into ballot-major contest order.
+static int contest_aggregates(eg_ctx* c, const ManShape& M, const ContestTabs& T, size_t nbc, const uint32_t* elems,
+                              uint32_t* agg) {
+  if (M.uniform)
+    return run_prod(c, elems, GroupMap{2, (uint32_t)M.nc, 1, 2 * M.uspc, (uint32_t)(2 * M.nsel)}, nbc * M.nc * 2,
+                    M.uspc, 2, agg);
+  for (size_t ci = 0; ci < M.cls.size(); ++ci) {
+    const size_t period = M.cls[ci].n * 2;
+    const int rc = run_prod_tab(c, elems, T.in[ci], period, 2 * M.nsel, nbc * period, M.cls[ci].spc, 2, agg,
+                                T.out[ci], 2 * M.nc);
     if (rc) return rc;
-    const uint32_t *jA = jv[0], *jB = jv[1], *jCA = jv[2], *jCB = jv[3];
-    // The selection jobs keep their comb powers y_k = alpha^(2^(52k)) (YA, YB); the contest
-    // aggregates A = prod alpha, B = prod beta then get theirs as products over the contest
-    // (4 x (spc-1) MM instead of 208 squarings; the contest comb costs ~150 MM, not 329).
-    // The alpha / beta jobs always run the comb (two column blocks): its squaring chain to
-    // B^(2^234) runs on to the residue test's B^(2^256) (EG_NO_COMB only switches the contest
-    // and trustee jobs to the 4-bit window).
-    const bool gat = c->use_comb != 0;
-    uint32_t *YA = nullptr, *YB = nullptr, *RZ = nullptr;
-    if (gat) {
-      if ((rc = ws_get(c, W_YA, ns * (kCombH - 1) * kW * 4, (void**)&YA))) return rc;
-      if ((rc = ws_get(c, W_YB, ns * (kCombH - 1) * kW * 4, (void**)&YB))) return rc;
-    }
-    // residue-test pairs (z, w) of every alpha, then every beta (4 device elements per selection)
-    if ((rc = ws_get(c, W_RZ, ns * 4 * kW * 4, (void**)&RZ))) return rc;
-    // Three launches: (1) alpha + the first xb beta jobs (xb fills launch 1's last round of
-    // resident workgroups), (2) the other beta jobs + every contest-a job (which needs only the
-    // alpha y_k; the short jobs fill launch 2's last rounds), (3) contest b (which needs the
-    // beta y_k).  With EG_CB_EARLY=1 launch 2 also takes the contest-b jobs whose betas all ran
-    // in launch 1 (k_pow's third job population).
-    // the selection jobs' comb: 4 rows x 3 blocks (22 columns, three 16-entry tables: 33 subset
-    // products, 21 squarings + 63 multiplies per exponent) or, with EG_SEL_COMB=52, round 2's
-    // 5 rows x 2 blocks (26 columns, two 32-entry tables: 52 + 2 x (25 + 51)); every block's
-    // bases come from the residue chain.  4 x 3 is 3 MM fewer per job, 0.4% more ballots per
-    // shader clock and a 0.6% higher clock (25% less comb-table traffic) in a same-box A/B
-    // (profiles/r03r_ab_sel43.log)
-    const uint32_t srows = c->sel_rows, sblocks = c->sel_blocks;
-    PowShape SA{};  // alpha: a0 = alpha^c0 g^v0, a1 = alpha^c1 g^v1  (comb shared by c0, c1)
-    SA.has_base = 1; SA.nout = 2; SA.nfb[0] = 1; SA.nfb[1] = 1; SA.exp_bytes = 32; SA.comb = 1; SA.resid = 1;
-    SA.rows = srows; SA.blocks = sblocks; SA.tab[0][0] = 0; SA.tab[1][0] = 0;
-    PowShape SB{};  // beta: b0 = beta^c0 K^v0, b1 = beta^c1 K^v1 g^-c1  (comb shared by c0, c1)
-    SB.has_base = 1; SB.nout = 2; SB.nfb[0] = 1; SB.nfb[1] = 2; SB.exp_bytes = 32; SB.comb = 1; SB.resid = 1;
-    SB.rows = srows; SB.blocks = sblocks; SB.tab[0][0] = 1; SB.tab[1][0] = 1; SB.tab[1][1] = 0;
-    PowShape SCA{};  // contest a = A^c g^v
-    SCA.has_base = 1; SCA.nout = 1; SCA.nfb[0] = 1; SCA.exp_bytes = 32; SCA.tab[0][0] = 0;
-    SCA.comb = gat ? 1u : 0u; SCA.gather = gat ? (uint32_t)spc : 0u;
-    PowShape SCB{};  // contest b = B^c K^v g^-Lc
-    SCB.has_base = 1; SCB.nout = 1; SCB.nfb[0] = 2; SCB.exp_bytes = 32; SCB.tab[0][0] = 1; SCB.tab[0][1] = 0;
-    SCB.comb = gat ? 1u : 0u; SCB.gather = gat ? (uint32_t)spc : 0u;
-    size_t xb = 0;
-    size_t slots = c->pow_slots;
-    if (const char* ov = getenv("EG_POW_SLOTS")) slots = (size_t)strtoull(ov, nullptr, 10);  // test override
-    // EG_CB_EARLY=1 (opt-in, measured slower): launch 1 also takes the betas of every contest
-    // whose contest-b job can then ride in launch 2, so launch 3 shrinks to EG_L3_WAVES waves
-    // per SIMD.  In an interleaved A/B on one box (four rounds, MM per shader clock from the
-    // in-kernel clock) it ran 0.4-0.5% SLOWER than the default split, although it cuts launch 3
-    // from 10.8 to ~5 ms (profiles/r03n_ab_l3clock.log); the default is the round-2 split below.
-    const char* cbe = getenv("EG_CB_EARLY");
-    const bool cb_early = cbe && cbe[0] == '1';
-    if (slots) {
-      auto last_blocks = [](size_t n) {  // workgroups of the last k_pow sub-launch of n jobs
-        return n ? (size_t)grid_for(n - (n - 1) / kPowMaxJobs * kPowMaxJobs) : 0;
-      };
-      // launch 3 (contest b after the contests launch 1 covers) within two waves per SIMD
-      // (EG_L3_WAVES, 1 .. the occupancy; a lone round of 172-MM jobs at 3 waves/SIMD takes
-      // ~5 ms, at 2 its jobs finish in about two thirds of that): at least (ncn - that many
-      // jobs) contests' betas in launch 1, rounded to whole workgroups
-      uint32_t l3w = std::min(2u, c->pow_wps);
-      if (const char* lw = getenv("EG_L3_WAVES")) l3w = (uint32_t)std::max(1, std::min((int)c->pow_wps, atoi(lw)));
-      const size_t l3_jobs = slots * kGroupsPerBlock * l3w / c->pow_wps;
-      size_t x0 = cb_early && ncn > l3_jobs ? (ncn - l3_jobs) * spc : 0;
-      x0 = std::min(ns, (x0 + kGroupsPerBlock - 1) / kGroupsPerBlock * kGroupsPerBlock);
-      // the beta head rides with alpha's last sub-launch: keep that launch within
-      // kPowTailJobs jobs (its k_pow scratch, 40 KB per job; a 120-selection chunk would
-      // otherwise put 1.8M beta jobs there), the rest of contest b then stays in launch 3
-      const size_t a_last = ns ? ns - (ns - 1) / kPowMaxJobs * kPowMaxJobs : 0;
-      const size_t cap = a_last < kPowTailJobs ? (kPowTailJobs - a_last) / kGroupsPerBlock * kGroupsPerBlock : 0;
-      x0 = std::min(x0, cap);
-      // then fill launch 1's last round (the beta part rides with alpha's last sub-launch)
-      const size_t used = last_blocks(ns) + x0 / kGroupsPerBlock;
-      const size_t fill1 = (slots - used % slots) % slots;
-      xb = std::min(ns, x0 + fill1 * kGroupsPerBlock);
-    }
-    const size_t jc = cb_early ? std::min(ncn, xb / spc) : 0;  // contests whose betas all run in launch 1
-    if (const char* dbg = getenv("EG_DEBUG_SCHED"); dbg && dbg[0] == '1')
-      fprintf(stderr, "eg verify schedule: ns %zu ncn %zu slots %zu waves/SIMD %u: beta head %zu, early contest b %zu\n",
-              ns, ncn, slots, c->pow_wps, xb, jc);
-    {
-      PowTail T{};  // the first xb beta jobs fill launch 1's last round
-      T.S = SB; T.jobs = jB; T.njobs = xb; T.yout = YB; T.rout = RZ + ns * 2 * kW;
-      if ((rc = launch_pow(c, SA, jA, ns, E, SC, COMM, G, K, YA, nullptr, &T, RZ))) return rc;
-    }
-    {
-      PowTail T{};  // contest a depends only on the alpha launch -> fills this launch's tail
-      T.S = SCA; T.jobs = jCA; T.njobs = ncn; T.ygat = YA;
-      PowTail T2{};  // contest b of the contests whose betas ran in launch 1
-      T2.S = SCB; T2.jobs = jCB; T2.njobs = jc; T2.ygat = YB;
-      if ((rc = launch_pow(c, SB, jB + xb * kJobWords, ns - xb, E, SC, COMM, G, K, YB + xb * (kCombH - 1) * kW,
-                           nullptr, &T, RZ + (ns + xb) * 2 * kW, false, nullptr, nullptr, &T2)))
-        return rc;
-    }
-    // alpha^q == 1 and beta^q == 1 (valid residues) fold into the range flags the hash check reads
-    LAUNCH_F(c, k_resid_check, dim3(grid_for(ns)), c->d, RZ, (uint32_t)ns, LTP, 2u);
-    LAUNCH_F(c, k_resid_check, dim3(grid_for(ns)), c->d, RZ + ns * 2 * kW, (uint32_t)ns, LTP + 1, 2u);
-    HIPCHK(hipGetLastError());
-    // The contest proof's message (A, B) = (prod alpha, prod beta) is valid when every selection's
-    // alpha (beta) is: the AND of the selections' range + residue flags (k_contest_flags), no
-    // products -- a contest holding an invalid selection is rejected together with it.
-    uint8_t* CRF = nullptr;  // (A, B) flags per contest
-    if ((rc = ws_get(c, W_CRF, ncn * 2, (void**)&CRF))) return rc;
-    hipLaunchKernelGGL(k_contest_flags, dim3(tgrid(ncn * 2)), dim3(256), 0, c->stream, LTP, (uint32_t)ncn,
-                       (uint32_t)spc, CRF);
-    HIPCHK(hipGetLastError());
-    if (jc < ncn) {
-      if ((rc = launch_pow(c, SCB, jCB + jc * kJobWords, ncn - jc, E, SC, COMM, G, K, nullptr, YB))) return rc;
-    }
-    // 5. canonical bytes of commitments and contest aggregates
-    if ((rc = launch_export(c, COMM, ns * 4 + ncn * 2, COMM_BE))) return rc;
-    if ((rc = launch_export(c, CP, ncn * 2, CP_BE))) return rc;
-    // 6. Fiat-Shamir checks
-    // (the challenges come from the caller's proofs: SC's may be negated, EG_RESPONSE_PLUS)
-    if ((rc = launch_hash(c, (uint32_t)ns,
-                          preimage(c, {HashSrc{cts, 512, 1024}, HashSrc{cts + 512, 512, 1024}},
-                                   {HashSrc{COMM_BE, 512, 2048}, HashSrc{COMM_BE + 512, 512, 2048},
-                                    HashSrc{COMM_BE + 1024, 512, 2048}, HashSrc{COMM_BE + 1536, 512, 2048}},
-                                   key_src(c)),
-                          d_rproof, 4, 0, 2, OKR, LTP, 2, d_ok_sel, nullptr)))
-      return rc;
-    const uint8_t* CC_BE = COMM_BE + ns * 4 * 512;
-    if ((rc = launch_hash(c, (uint32_t)ncn,
-                          preimage(c, {HashSrc{CP_BE, 512, 1024}, HashSrc{CP_BE + 512, 512, 1024}},
-                                   {HashSrc{CC_BE, 512, 1024}, HashSrc{CC_BE + 512, 512, 1024}}, key_src(c)),
-                          d_cproof, 2, 0, kNone, OKC, CRF, 2, d_ok_con, nullptr)))
-      return rc;
-    // 7. tally over this chunk's cast ballots (real selections only)
-    if (tally) {
-      uint32_t* T = first ? tally : tally + nreal * 2 * kW;
-      if ((rc = run_prod(c, E, GroupMap{2, (uint32_t)nrs, 1, 2, (uint32_t)(2 * spc)}, nreal * 2, nbc, nsel * 2, T,
-                         d_cast)))
-        return rc;
-      if (!first) {
-        LAUNCH_F(c, k_mul, dim3(grid_for(nreal * 2)), c->d, tally, 1u, T, 1u,
-                           (uint32_t)(nreal * 2), tally, 1u);
-        HIPCHK(hipGetLastError());
-      }
-    }
   }
   return EG_OK;
 }
+// The contest proofs' scalars (c, v) x ncn at sc: range flags -> okc, the exponents -L_k c -> negL
+static void contest_scalars(eg_ctx* c, const ManShape& M, const ContestTabs& T, uint8_t* sc, size_t ncn, uint8_t* negL,
+                            uint8_t* okc) {
+  if (M.uniform)
+    hipLaunchKernelGGL(k_scalar_prep, dim3(tgrid(ncn)), dim3(256), 0, c->stream, c->d_q, sc, (uint32_t)ncn, 2u, 0u,
+                       M.ulimit, negL, okc, c->resp_plus, 0x1u);
+  else
+    hipLaunchKernelGGL(k_scalar_prep_tab, dim3(tgrid(ncn)), dim3(256), 0, c->stream, c->d_q, sc, (uint32_t)ncn, 2u, 0u,
+                       T.limit, (uint32_t)M.nc, negL, okc, c->resp_plus, 0x1u);
+}
+// (A, B) flags per contest: the AND of its selections' range + residue flags
+static void contest_flags(eg_ctx* c, const ManShape& M, const ContestTabs& T, const uint8_t* ltp, size_t ncn,
+                          uint8_t* crf) {
+  if (M.uniform)
+    hipLaunchKernelGGL(k_contest_flags, dim3(tgrid(ncn * 2)), dim3(256), 0, c->stream, ltp, (uint32_t)ncn, M.uspc,
+                       crf);
+  else
+    hipLaunchKernelGGL(k_contest_flags_seg, dim3(tgrid(ncn * 2)), dim3(256), 0, c->stream, ltp, (uint32_t)ncn,
+                       (uint32_t)M.nc, (uint32_t)M.nsel, T.first, T.spc, crf);
+}
+// the sum of each contest's selection nonces R (the encryptor's scalars sc) -> rsum
+static void nonce_sums(eg_ctx* c, const ManShape& M, const ContestTabs& T, const uint8_t* sc, size_t ncn,
+                       uint8_t* rsum) {
+  if (M.uniform)
+    hipLaunchKernelGGL(k_enc_rsum, dim3(tgrid(ncn)), dim3(256), 0, c->stream, c->d_q, sc, (uint32_t)ncn, M.uspc, rsum);
+  else
+    hipLaunchKernelGGL(k_enc_rsum_seg, dim3(tgrid(ncn)), dim3(256), 0, c->stream, c->d_q, sc, (uint32_t)ncn,
+                       (uint32_t)M.nc, (uint32_t)M.nsel, T.first, T.spc, rsum);
+}
+// products over the nbc ballots with cast[b] != 0 (all: cast == nullptr) of every real
+// selection's (alpha, beta) -> out[nreal * 2]
+static int chunk_tally(eg_ctx* c, const ManShape& M, const ContestTabs& T, size_t nbc, const uint32_t* elems,
+                       uint32_t* out, const uint8_t* d_cast) {
+  if (M.uniform)
+    return run_prod(c, elems, GroupMap{2, M.uspc - M.uph, 1, 2, 2 * M.uspc}, M.nreal * 2, nbc, M.nsel * 2, out, d_cast);
+  return run_prod_tab(c, elems, T.tally, M.nreal * 2, 0, M.nreal * 2, nbc, M.nsel * 2, out, nullptr, 0, d_cast);
+}
 
-static int verify_prologue_locked(eg_ctx* c, const uint8_t* qbar_be, size_t nc, size_t spc, size_t ph) {
-  if (!manifest_ok(nc, spc) || ph >= spc) return fail(EG_ERR_ARG, "bad manifest shape");
-  if (!c->Ktab) return fail(EG_ERR_STATE, "election key not set (eg_set_election_key)");
-  HIPCHK(hipMemcpyAsync(c->d_qbar, qbar_be, 32, hipMemcpyHostToDevice, c->stream));
+// ---------------------------------------------------------------------------------
+// verification + tally
+// ---------------------------------------------------------------------------------
+// The verifier's scalar space (32-byte rows): the range proofs (c0, v0, c1, v1) x ns, the contest
+// proofs (c, v) x ncn, then the derived exponents -c1 x ns and -L c x ncn.  Elements: the
+// ciphertexts (ns x 2), then the aggregates (ncn x 2); commitments: ns x 4, then ncn x 2.
+struct VerifyLayout {
+  size_t ns, ncn, off_c, off_neg, off_negL;
+  VerifyLayout(const ManShape& M, size_t nbc)
+      : ns(nbc * M.nsel), ncn(nbc * M.nc), off_c(ns * 4), off_neg(off_c + ncn * 2), off_negL(off_neg + ns) {}
+};
+// the alpha (beta == false) or beta jobs of ns selections
+static std::vector<uint32_t> verify_sel_jobs(const VerifyLayout& V, bool beta) {
+  auto J = new_jobs(V.ns);
+  for (size_t i = 0; i < V.ns; ++i) {
+    uint32_t* x = &J[i * kJobWords];
+    const uint32_t c0 = (uint32_t)(i * 4), v0 = c0 + 1, c1 = c0 + 2, v1 = c0 + 3, e = beta ? 1u : 0u;
+    x[0] = (uint32_t)(i * 2) + e; x[1] = c0; x[2] = c1; x[3] = c0 + e; x[4] = c1 + e; x[5] = v0; x[7] = v1;
+    if (beta) x[8] = (uint32_t)(V.off_neg + i);
+  }
+  return J;
+}
+// the contest a (b == false) or contest b jobs of class C, ballot-major: job bi * C.n + mi
+static std::vector<uint32_t> verify_contest_jobs(const ManShape& M, const ManShape::Class& C, const VerifyLayout& V,
+                                                 size_t nbc, bool b) {
+  auto J = new_jobs(nbc * C.n);
+  for (size_t bi = 0; bi < nbc; ++bi)
+    for (size_t mi = 0; mi < C.n; ++mi) {
+      const uint32_t k = M.member(C, mi), e = b ? 1u : 0u;
+      const size_t j = bi * M.nc + k;  // the contest's place in every ballot-major array
+      uint32_t* x = &J[(bi * C.n + mi) * kJobWords];
+      const uint32_t cc = (uint32_t)(V.off_c + j * 2);
+      x[0] = (uint32_t)(V.ns * 2 + j * 2) + e; x[1] = cc; x[3] = (uint32_t)(V.ns * 4 + j * 2) + e; x[5] = cc + 1;
+      if (b) x[6] = (uint32_t)(V.off_negL + j);
+      x[2] = (uint32_t)(bi * M.nsel + M.first_of(k));  // gather: the contest's first selection job (y_k source)
+    }
+  return J;
+}
+
+// One k_pow job population, and one launch_pow call of the contest populations: a main part and
+// up to two tails.
+struct Pop {
+  PowShape S;
+  const uint32_t* jobs;
+  size_t n;
+  const uint32_t* ygat;
+  Pop part(size_t off, size_t cnt) const { return Pop{S, jobs + off * kJobWords, cnt, ygat}; }
+  PowTail tail() const {
+    PowTail T{};
+    T.S = S; T.jobs = jobs; T.njobs = n; T.ygat = ygat;
+    return T;
+  }
+};
+struct PowLaunch {
+  Pop main;
+  std::vector<Pop> tails;
+};
+// The verifier's k_pow launches.  Launch 1 is alpha with the first xb beta jobs as its tail,
+// launch 2 the other betas with `l2` as tails, then `later`, one launch_pow call each.
+struct VerifyPlan {
+  size_t xb = 0;
+  std::vector<Pop> l2;
+  std::vector<PowLaunch> later;
+};
+
+// The beta head: x0 beta jobs (rounded to whole workgroups) plus as many as fill launch 1's last
+// round of `slots` resident workgroups.
+static size_t beta_head(size_t ns, size_t slots, size_t x0) {
+  if (!slots) return 0;
+  auto last_blocks = [](size_t n) {  // workgroups of the last k_pow sub-launch of n jobs
+    return n ? (size_t)grid_for(n - (n - 1) / kPowMaxJobs * kPowMaxJobs) : 0;
+  };
+  x0 = std::min(ns, (x0 + kGroupsPerBlock - 1) / kGroupsPerBlock * kGroupsPerBlock);
+  // the beta head rides with alpha's last sub-launch: keep that launch within
+  // kPowTailJobs jobs (its k_pow scratch, 40 KB per job; a 120-selection chunk would
+  // otherwise put 1.8M beta jobs there), the rest of contest b then stays in launch 3
+  const size_t a_last = ns ? ns - (ns - 1) / kPowMaxJobs * kPowMaxJobs : 0;
+  const size_t cap = a_last < kPowTailJobs ? (kPowTailJobs - a_last) / kGroupsPerBlock * kGroupsPerBlock : 0;
+  x0 = std::min(x0, cap);
+  // then fill launch 1's last round (the beta part rides with alpha's last sub-launch)
+  const size_t used = last_blocks(ns) + x0 / kGroupsPerBlock;
+  const size_t fill1 = (slots - used % slots) % slots;
+  return std::min(ns, x0 + fill1 * kGroupsPerBlock);
+}
+
+// pa / pb: the contest a = A^c g^v populations (need the alpha y_k: any launch after 1) and the
+// contest b = B^c K^v g^-Lc populations (need the beta y_k: any launch after 2), one per class.
+// Two rules, because the uniform entry points' plan is the measured one of the benchmark:
+//   * uniform: three launches.  Launch 2 takes EVERY contest-a job as one tail, whatever their
+//     number (a 16,384 x 20-contest chunk's 327,680 ride as one), launch 3 is contest b.  With
+//     EG_CB_EARLY=1 (opt-in, measured slower) launch 1 also takes the betas of every contest
+//     whose contest-b job can then ride in launch 2, so launch 3 shrinks to EG_L3_WAVES waves per
+//     SIMD.  In an interleaved A/B on one box (four rounds, MM per shader clock from the
+//     in-kernel clock) it ran 0.4-0.5% SLOWER than the default split, although it cuts launch 3
+//     from 10.8 to ~5 ms (profiles/r03n_ab_l3clock.log).
+//   * table-addressed: launch 2 takes up to two contest-a populations as its tails; what is left
+//     of contest a and every contest-b population follow three to a launch.  A tail is never
+//     split into sub-launches, so only populations of at most kPowMaxJobs jobs ride as one.  At
+//     most 2 + (C - 2) + C <= 2 + 2 C launch_pow calls for C classes.  EG_CB_EARLY is ignored.
+static VerifyPlan plan_pow_launches(const eg_ctx* c, const ManShape& M, size_t ns, size_t ncn,
+                                    const std::vector<Pop>& pa, const std::vector<Pop>& pb) {
+  VerifyPlan P;
+  size_t slots = c->pow_slots;
+  if (const char* ov = getenv("EG_POW_SLOTS")) slots = (size_t)strtoull(ov, nullptr, 10);  // test override
+  const char* dbg = getenv("EG_DEBUG_SCHED");
+  const bool debug = dbg && dbg[0] == '1';
+  if (M.uniform) {
+    const char* cbe = getenv("EG_CB_EARLY");
+    const bool cb_early = cbe && cbe[0] == '1';
+    // launch 3 (contest b after the contests launch 1 covers) within two waves per SIMD
+    // (EG_L3_WAVES, 1 .. the occupancy; a lone round of 172-MM jobs at 3 waves/SIMD takes
+    // ~5 ms, at 2 its jobs finish in about two thirds of that): at least (ncn - that many
+    // jobs) contests' betas in launch 1
+    size_t x0 = 0;
+    if (slots && cb_early) {
+      uint32_t l3w = std::min(2u, c->pow_wps);
+      if (const char* lw = getenv("EG_L3_WAVES")) l3w = (uint32_t)std::max(1, std::min((int)c->pow_wps, atoi(lw)));
+      const size_t l3_jobs = slots * kGroupsPerBlock * l3w / c->pow_wps;
+      if (ncn > l3_jobs) x0 = (ncn - l3_jobs) * M.uspc;
+    }
+    P.xb = beta_head(ns, slots, x0);
+    const size_t jc = cb_early ? std::min(ncn, P.xb / M.uspc) : 0;  // contests whose betas all run in launch 1
+    if (debug)
+      fprintf(stderr, "eg verify schedule: ns %zu ncn %zu slots %zu waves/SIMD %u: beta head %zu, early contest b %zu\n",
+              ns, ncn, slots, c->pow_wps, P.xb, jc);
+    P.l2 = {pa[0], pb[0].part(0, jc)};
+    if (jc < ncn) P.later.push_back(PowLaunch{pb[0].part(jc, ncn - jc), {}});
+    return P;
+  }
+  P.xb = beta_head(ns, slots, 0);
+  std::vector<Pop> rest;
+  for (const Pop& p : pa) {
+    if (P.l2.size() < 2 && p.n <= kPowMaxJobs) P.l2.push_back(p);
+    else rest.push_back(p);
+  }
+  if (debug)
+    fprintf(stderr, "eg verify schedule (manifest): ns %zu ncn %zu classes %zu slots %zu: beta head %zu, "
+                    "contest a in launch 2: %zu\n", ns, ncn, M.cls.size(), slots, P.xb, P.l2.size());
+  rest.insert(rest.end(), pb.begin(), pb.end());
+  for (size_t i = 0; i < rest.size();) {
+    PowLaunch L{rest[i++], {}};
+    while (L.tails.size() < 2 && i < rest.size() && rest[i].n <= kPowMaxJobs) L.tails.push_back(rest[i++]);
+    P.later.push_back(std::move(L));
+  }
+  return P;
+}
+
+// One chunk of <= ballot_chunk(nsel) ballots: every proof of ballots [0, nbc) of the given device
+// arrays, and (tally != nullptr) their per-selection products, written to tally (first
+// chunk) or multiplied into it.  d_qbar and the key tables are set by the caller.
+// cast (optional, nbc bytes on the device): only ballots with cast[b] != 0 enter the tally; the
+// others (spoiled ballots, RunRemoteDecryptor.java:264-269) are verified but not tallied.
+static int verify_chunk_locked(eg_ctx* c, const ManShape& M, size_t nbc, const uint8_t* cts, const uint8_t* d_rproof,
+                               const uint8_t* d_cproof, const uint8_t* d_cast, uint8_t* d_ok_sel, uint8_t* d_ok_con,
+                               uint32_t* tally, bool first) {
+  const FbTab G = c->gtab->tab(), K = c->Ktab->tab();
+  const VerifyLayout V(M, nbc);
+  const size_t ns = V.ns, ncn = V.ncn, nreal = M.nreal, ncls = M.cls.size();
+  int rc;
+  uint32_t *E = nullptr, *COMM = nullptr;
+  uint8_t *LTP = nullptr, *SC = nullptr, *OKR = nullptr, *OKC = nullptr, *COMM_BE = nullptr, *CP_BE = nullptr;
+  if ((rc = ws_get(c, W_E0, (ns * 2 + ncn * 2) * kW * 4, (void**)&E))) return rc;
+  if ((rc = ws_get(c, W_E1, (ns * 4 + ncn * 2) * kW * 4, (void**)&COMM))) return rc;
+  if ((rc = ws_get(c, W_FLAGS, ns * 2, (void**)&LTP))) return rc;
+  if ((rc = ws_get(c, W_SCAL, (V.off_negL + ncn) * 32, (void**)&SC))) return rc;
+  if ((rc = ws_get(c, W_OK0, ns, (void**)&OKR))) return rc;
+  if ((rc = ws_get(c, W_OK1, ncn, (void**)&OKC))) return rc;
+  if ((rc = ws_get(c, W_BE0, (ns * 4 + ncn * 2) * 512, (void**)&COMM_BE))) return rc;
+  if ((rc = ws_get(c, W_BE1, ncn * 2 * 512, (void**)&CP_BE))) return rc;
+  // The chunk's tables, one cached set (a second set could be freed by the first's cache_bound):
+  // the contest layer's, the selection jobs, and per class the contest jobs.
+  ContestTabs T(M);
+  const uint32_t *jA = nullptr, *jB = nullptr;
+  std::vector<const uint32_t*> jCA(ncls, nullptr), jCB(ncls, nullptr);
+  TableList L;
+  add_contest_tables(L, M, T, true);
+  L.add("A", &jA, [&]() { return verify_sel_jobs(V, false); });
+  L.add("B", &jB, [&]() { return verify_sel_jobs(V, true); });
+  for (size_t ci = 0; ci < ncls; ++ci) {
+    const ManShape::Class& C = M.cls[ci];
+    add_class_tables(L, M, T, ci);
+    L.add("CA" + C.tag, &jCA[ci], [&M, &C, &V, nbc]() { return verify_contest_jobs(M, C, V, nbc, false); });
+    L.add("CB" + C.tag, &jCB[ci], [&M, &C, &V, nbc]() { return verify_contest_jobs(M, C, V, nbc, true); });
+  }
+  if ((rc = fetch_tables(c, M.fam + "v/" + std::to_string(nbc) + "/" + M.key, L))) return rc;
+  // 1. import ciphertexts (range flags alpha, beta < p)
+  if ((rc = launch_import(c, cts, ns * 2, E, LTP))) return rc;
+  // 2. scalars: proofs + derived exponents (-c1, -L c) + range flags
+  HIPCHK(hipMemcpyAsync(SC, d_rproof, ns * 128, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(SC + V.off_c * 32, d_cproof, ncn * 64, hipMemcpyDeviceToDevice, c->stream));
+  // plus convention: c0, c1 and c negated in place (the comb exponents), the g terms take +c1, +L c
+  hipLaunchKernelGGL(k_scalar_prep, dim3(tgrid(ns)), dim3(256), 0, c->stream, c->d_q, SC, (uint32_t)ns, 4u, 2u, 1u,
+                     SC + V.off_neg * 32, OKR, c->resp_plus, 0x5u);
+  contest_scalars(c, M, T, SC + V.off_c * 32, ncn, SC + V.off_negL * 32, OKC);
+  HIPCHK(hipGetLastError());
+  // 3. contest aggregates A = prod alpha, B = prod beta -> E[ns*2 + j*2 + {0,1}]
+  uint32_t* CP = E + ns * 2 * kW;
+  if ((rc = contest_aggregates(c, M, T, nbc, E, CP))) return rc;
+  // 4. commitments
+  // The selection jobs keep their comb powers y_k = alpha^(2^(52k)) (YA, YB); the contest
+  // aggregates A = prod alpha, B = prod beta then get theirs as products over the contest
+  // (4 x (spc-1) MM instead of 208 squarings; the contest comb costs ~150 MM, not 329).
+  // The alpha / beta jobs always run the comb (two column blocks): its squaring chain to
+  // B^(2^234) runs on to the residue test's B^(2^256) (EG_NO_COMB only switches the contest
+  // and trustee jobs to the 4-bit window).
+  const bool gat = c->use_comb != 0;
+  uint32_t *YA = nullptr, *YB = nullptr, *RZ = nullptr;
+  if (gat) {
+    if ((rc = ws_get(c, W_YA, ns * (kCombH - 1) * kW * 4, (void**)&YA))) return rc;
+    if ((rc = ws_get(c, W_YB, ns * (kCombH - 1) * kW * 4, (void**)&YB))) return rc;
+  }
+  // residue-test pairs (z, w) of every alpha, then every beta (4 device elements per selection)
+  if ((rc = ws_get(c, W_RZ, ns * 4 * kW * 4, (void**)&RZ))) return rc;
+  // the selection jobs' comb: 4 rows x 3 blocks (22 columns, three 16-entry tables: 33 subset
+  // products, 21 squarings + 63 multiplies per exponent) or, with EG_SEL_COMB=52, round 2's
+  // 5 rows x 2 blocks (26 columns, two 32-entry tables: 52 + 2 x (25 + 51)); every block's
+  // bases come from the residue chain.  4 x 3 is 3 MM fewer per job, 0.4% more ballots per
+  // shader clock and a 0.6% higher clock (25% less comb-table traffic) in a same-box A/B
+  // (profiles/r03r_ab_sel43.log)
+  const uint32_t srows = c->sel_rows, sblocks = c->sel_blocks;
+  PowShape SA{};  // alpha: a0 = alpha^c0 g^v0, a1 = alpha^c1 g^v1  (comb shared by c0, c1)
+  SA.has_base = 1; SA.nout = 2; SA.nfb[0] = 1; SA.nfb[1] = 1; SA.exp_bytes = 32; SA.comb = 1; SA.resid = 1;
+  SA.rows = srows; SA.blocks = sblocks; SA.tab[0][0] = 0; SA.tab[1][0] = 0;
+  PowShape SB{};  // beta: b0 = beta^c0 K^v0, b1 = beta^c1 K^v1 g^-c1  (comb shared by c0, c1)
+  SB.has_base = 1; SB.nout = 2; SB.nfb[0] = 1; SB.nfb[1] = 2; SB.exp_bytes = 32; SB.comb = 1; SB.resid = 1;
+  SB.rows = srows; SB.blocks = sblocks; SB.tab[0][0] = 1; SB.tab[1][0] = 1; SB.tab[1][1] = 0;
+  std::vector<Pop> pa, pb;
+  for (size_t ci = 0; ci < ncls; ++ci) {
+    const uint32_t gather = gat ? M.cls[ci].spc : 0u;
+    const size_t n = nbc * M.cls[ci].n;
+    PowShape SCA{};  // contest a = A^c g^v
+    SCA.has_base = 1; SCA.nout = 1; SCA.nfb[0] = 1; SCA.exp_bytes = 32; SCA.tab[0][0] = 0;
+    SCA.comb = gat ? 1u : 0u; SCA.gather = gather;
+    PowShape SCB{};  // contest b = B^c K^v g^-Lc
+    SCB.has_base = 1; SCB.nout = 1; SCB.nfb[0] = 2; SCB.exp_bytes = 32; SCB.tab[0][0] = 1; SCB.tab[0][1] = 0;
+    SCB.comb = gat ? 1u : 0u; SCB.gather = gather;
+    pa.push_back(Pop{SCA, jCA[ci], n, YA});
+    pb.push_back(Pop{SCB, jCB[ci], n, YB});
+  }
+  const VerifyPlan P = plan_pow_launches(c, M, ns, ncn, pa, pb);
+  const size_t xb = P.xb;
+  auto launch = [&](const PowShape& S, const uint32_t* jobs, size_t n, uint32_t* yout, const uint32_t* ygat,
+                    uint32_t* rout, const std::vector<PowTail>& tl) {
+    return launch_pow(c, S, jobs, n, E, SC, COMM, G, K, yout, ygat, tl.size() > 0 ? &tl[0] : nullptr, rout, false,
+                      nullptr, nullptr, tl.size() > 1 ? &tl[1] : nullptr);
+  };
+  auto tails_of = [](const std::vector<Pop>& pops) {
+    std::vector<PowTail> tl;
+    for (const Pop& p : pops) tl.push_back(p.tail());
+    return tl;
+  };
+  {
+    PowTail H{};  // the first xb beta jobs fill launch 1's last round
+    H.S = SB; H.jobs = jB; H.njobs = xb; H.yout = YB; H.rout = RZ + ns * 2 * kW;
+    if ((rc = launch(SA, jA, ns, YA, nullptr, RZ, {H}))) return rc;
+  }
+  if ((rc = launch(SB, jB + xb * kJobWords, ns - xb, gat ? YB + xb * (kCombH - 1) * kW : nullptr, nullptr,
+                   RZ + (ns + xb) * 2 * kW, tails_of(P.l2))))
+    return rc;
+  // alpha^q == 1 and beta^q == 1 (valid residues) fold into the range flags the hash check reads
+  LAUNCH_F(c, k_resid_check, dim3(grid_for(ns)), c->d, RZ, (uint32_t)ns, LTP, 2u);
+  LAUNCH_F(c, k_resid_check, dim3(grid_for(ns)), c->d, RZ + ns * 2 * kW, (uint32_t)ns, LTP + 1, 2u);
+  HIPCHK(hipGetLastError());
+  // The contest proof's message (A, B) = (prod alpha, prod beta) is valid when every selection's
+  // alpha (beta) is: the AND of the selections' range + residue flags, no products -- a contest
+  // holding an invalid selection is rejected together with it.
+  uint8_t* CRF = nullptr;
+  if ((rc = ws_get(c, W_CRF, ncn * 2, (void**)&CRF))) return rc;
+  contest_flags(c, M, T, LTP, ncn, CRF);
+  HIPCHK(hipGetLastError());
+  for (const PowLaunch& l : P.later)
+    if ((rc = launch(l.main.S, l.main.jobs, l.main.n, nullptr, l.main.ygat, nullptr, tails_of(l.tails)))) return rc;
+  // 5. canonical bytes of commitments and contest aggregates
+  if ((rc = launch_export(c, COMM, ns * 4 + ncn * 2, COMM_BE))) return rc;
+  if ((rc = launch_export(c, CP, ncn * 2, CP_BE))) return rc;
+  // 6. Fiat-Shamir checks
+  // (the challenges come from the caller's proofs: SC's may be negated, EG_RESPONSE_PLUS)
+  if ((rc = launch_hash(c, (uint32_t)ns,
+                        preimage(c, {HashSrc{cts, 512, 1024}, HashSrc{cts + 512, 512, 1024}},
+                                 {HashSrc{COMM_BE, 512, 2048}, HashSrc{COMM_BE + 512, 512, 2048},
+                                  HashSrc{COMM_BE + 1024, 512, 2048}, HashSrc{COMM_BE + 1536, 512, 2048}},
+                                 key_src(c)),
+                        d_rproof, 4, 0, 2, OKR, LTP, 2, d_ok_sel, nullptr)))
+    return rc;
+  const uint8_t* CC_BE = COMM_BE + ns * 4 * 512;
+  if ((rc = launch_hash(c, (uint32_t)ncn,
+                        preimage(c, {HashSrc{CP_BE, 512, 1024}, HashSrc{CP_BE + 512, 512, 1024}},
+                                 {HashSrc{CC_BE, 512, 1024}, HashSrc{CC_BE + 512, 512, 1024}}, key_src(c)),
+                        d_cproof, 2, 0, kNone, OKC, CRF, 2, d_ok_con, nullptr)))
+    return rc;
+  // 7. tally over this chunk's cast ballots (real selections only)
+  if (tally) {
+    uint32_t* TP = first ? tally : tally + nreal * 2 * kW;
+    if ((rc = chunk_tally(c, M, T, nbc, E, TP, d_cast))) return rc;
+    if (!first) {
+      LAUNCH_F(c, k_mul, dim3(grid_for(nreal * 2)), c->d, tally, 1u, TP, 1u, (uint32_t)(nreal * 2), tally, 1u);
+      HIPCHK(hipGetLastError());
+    }
+  }
   return EG_OK;
 }
 
@@ -464,17 +716,13 @@ static void ones_be(uint8_t* out, size_t n) {
   for (size_t i = 0; i < n; ++i) out[i * 512 + 511] = 1;
 }
 
-extern "C" int eg_verify_ballots_dev(eg_ctx* c, const uint8_t K_be[512], const uint8_t qbar_be[32], size_t nb,
-                                     size_t nc, size_t spc, size_t ph, uint32_t limit, const uint8_t* d_cts,
-                                     const uint8_t* d_rproof, const uint8_t* d_cproof, const uint8_t* d_cast,
-                                     uint8_t* d_ok_sel, uint8_t* d_ok_con, uint8_t* d_tally_be) {
-  if (!c || !K_be || !qbar_be || (nb && (!d_cts || !d_rproof || !d_cproof || !d_ok_sel || !d_ok_con)))
-    return fail(EG_ERR_ARG, "null argument");
-  if (!manifest_ok(nc, spc) || ph >= spc) return fail(EG_ERR_ARG, "bad manifest shape");
-  Locked L(c);
+// The drivers below run under the caller's lock, after its argument checks and use_key_locked.
+// Device pointers in and out, chunk by chunk on the ctx stream.
+static int verify_dev_locked(eg_ctx* c, const ManShape& M, const uint8_t* qbar_be, size_t nb, const uint8_t* d_cts,
+                             const uint8_t* d_rproof, const uint8_t* d_cproof, const uint8_t* d_cast,
+                             uint8_t* d_ok_sel, uint8_t* d_ok_con, uint8_t* d_tally_be) {
   int rc;
-  if ((rc = use_key_locked(c, K_be))) return rc;
-  const size_t nsel = nc * spc, nreal = nc * (spc - ph);
+  const size_t nc = M.nc, nsel = M.nsel, nreal = M.nreal;
   if (!nb) {
     if (d_tally_be) {
       std::vector<uint8_t> one(nreal * 2 * 512);
@@ -484,13 +732,14 @@ extern "C" int eg_verify_ballots_dev(eg_ctx* c, const uint8_t K_be[512], const u
     }
     return EG_OK;
   }
-  if ((rc = verify_prologue_locked(c, qbar_be, nc, spc, ph))) return rc;
+  if (!c->Ktab) return fail(EG_ERR_STATE, "election key not set (eg_set_election_key)");
+  HIPCHK(hipMemcpyAsync(c->d_qbar, qbar_be, 32, hipMemcpyHostToDevice, c->stream));
   uint32_t* tally = nullptr;  // running tally (Montgomery) + one chunk's product, nreal*2 elements each
   if (d_tally_be && (rc = ws_get(c, W_E2, nreal * 2 * 2 * kW * 4, (void**)&tally))) return rc;
   const size_t chunk = ballot_chunk(nsel);
   for (size_t b0 = 0; b0 < nb; b0 += chunk) {
     const size_t nbc = std::min(chunk, nb - b0);
-    if ((rc = verify_chunk_locked(c, nbc, nc, spc, ph, limit, d_cts + b0 * nsel * 1024, d_rproof + b0 * nsel * 128,
+    if ((rc = verify_chunk_locked(c, M, nbc, d_cts + b0 * nsel * 1024, d_rproof + b0 * nsel * 128,
                                   d_cproof + b0 * nc * 64, d_cast ? d_cast + b0 : nullptr, d_ok_sel + b0 * nsel,
                                   d_ok_con + b0 * nc, tally, b0 == 0)))
       return rc;
@@ -509,27 +758,22 @@ static int ensure_copy_stream(eg_ctx* c) {
   return EG_OK;
 }
 
-extern "C" int eg_verify_ballots(eg_ctx* c, const uint8_t K_be[512], const uint8_t qbar_be[32], size_t nb, size_t nc,
-                                 size_t spc, size_t ph, uint32_t limit, const uint8_t* cts, const uint8_t* rproof,
-                                 const uint8_t* cproof, const uint8_t* cast, uint8_t* ok_sel, uint8_t* ok_con,
-                                 uint8_t* tally_be) {
-  if (!c || !K_be || !qbar_be || (nb && (!cts || !rproof || !cproof || !ok_sel || !ok_con)))
-    return fail(EG_ERR_ARG, "null argument");
-  if (!manifest_ok(nc, spc) || ph >= spc) return fail(EG_ERR_ARG, "bad manifest shape");
-  Locked L(c);
+// Host pointers, streamed in ballot_chunk(nsel)-ballot chunks through two upload buffers: chunk
+// k+1's wire input goes up on the ctx's copy stream while chunk k verifies on the ctx stream, so
+// the device holds two chunks of input (about 2 x 400 MB at 4x(5+1)) however many ballots the
+// caller passes.  Verdicts stay on the device until the end (a pageable D2H per chunk would block
+// the host before it can start the next upload).
+static int verify_host_locked(eg_ctx* c, const ManShape& M, const uint8_t* qbar_be, size_t nb, const uint8_t* cts,
+                              const uint8_t* rproof, const uint8_t* cproof, const uint8_t* cast, uint8_t* ok_sel,
+                              uint8_t* ok_con, uint8_t* tally_be) {
   int rc;
-  if ((rc = use_key_locked(c, K_be))) return rc;
-  const size_t nsel = nc * spc, nreal = nc * (spc - ph);
+  const size_t nc = M.nc, nsel = M.nsel, nreal = M.nreal;
   if (!nb) {
     if (tally_be) ones_be(tally_be, nreal * 2);
     return EG_OK;
   }
-  // Streamed in ballot_chunk(nsel)-ballot chunks through two upload buffers: chunk k+1's wire input
-  // goes up on the ctx's copy stream while chunk k verifies on the ctx stream, so the device
-  // holds two chunks of input (about 2 x 400 MB at 4x(5+1)) however many ballots the caller
-  // passes.  Verdicts stay on the device until the end (a pageable D2H per chunk would block
-  // the host before it can start the next upload).
-  if ((rc = verify_prologue_locked(c, qbar_be, nc, spc, ph))) return rc;
+  if (!c->Ktab) return fail(EG_ERR_STATE, "election key not set (eg_set_election_key)");
+  HIPCHK(hipMemcpyAsync(c->d_qbar, qbar_be, 32, hipMemcpyHostToDevice, c->stream));
   if ((rc = ensure_copy_stream(c))) return rc;
   const size_t chunk = ballot_chunk(nsel);
   uint32_t* tally = nullptr;
@@ -557,9 +801,8 @@ extern "C" int eg_verify_ballots(eg_ctx* c, const uint8_t K_be[512], const uint8
     HIPCHK(hipMemcpyAsync(up[u][2], cproof + b0 * nc * 64, nbc * nc * 64, hipMemcpyHostToDevice, c->copy));
     HIPCHK(hipEventRecord(c->up_ev[u], c->copy));
     HIPCHK(hipStreamWaitEvent(c->stream, c->up_ev[u], 0));
-    if ((rc = verify_chunk_locked(c, nbc, nc, spc, ph, limit, up[u][0], up[u][1], up[u][2],
-                                  d_cast ? d_cast + b0 : nullptr, d_oks + b0 * nsel, d_okc + b0 * nc, tally,
-                                  b0 == 0)))
+    if ((rc = verify_chunk_locked(c, M, nbc, up[u][0], up[u][1], up[u][2], d_cast ? d_cast + b0 : nullptr,
+                                  d_oks + b0 * nsel, d_okc + b0 * nc, tally, b0 == 0)))
       return rc;
     HIPCHK(hipEventRecord(c->done_ev[u], c->stream));
   }
@@ -573,6 +816,34 @@ extern "C" int eg_verify_ballots(eg_ctx* c, const uint8_t K_be[512], const uint8
   }
   HIPCHK(hipStreamSynchronize(c->stream));
   return EG_OK;
+}
+
+extern "C" int eg_verify_ballots_dev(eg_ctx* c, const uint8_t K_be[512], const uint8_t qbar_be[32], size_t nb,
+                                     size_t nc, size_t spc, size_t ph, uint32_t limit, const uint8_t* d_cts,
+                                     const uint8_t* d_rproof, const uint8_t* d_cproof, const uint8_t* d_cast,
+                                     uint8_t* d_ok_sel, uint8_t* d_ok_con, uint8_t* d_tally_be) {
+  if (!c || !K_be || !qbar_be || (nb && (!d_cts || !d_rproof || !d_cproof || !d_ok_sel || !d_ok_con)))
+    return fail(EG_ERR_ARG, "null argument");
+  if (!manifest_ok(nc, spc) || ph >= spc) return fail(EG_ERR_ARG, "bad manifest shape");
+  const ManShape M = uniform_shape(nc, spc, ph, limit);
+  Locked L(c);
+  int rc;
+  if ((rc = use_key_locked(c, K_be))) return rc;
+  return verify_dev_locked(c, M, qbar_be, nb, d_cts, d_rproof, d_cproof, d_cast, d_ok_sel, d_ok_con, d_tally_be);
+}
+
+extern "C" int eg_verify_ballots(eg_ctx* c, const uint8_t K_be[512], const uint8_t qbar_be[32], size_t nb, size_t nc,
+                                 size_t spc, size_t ph, uint32_t limit, const uint8_t* cts, const uint8_t* rproof,
+                                 const uint8_t* cproof, const uint8_t* cast, uint8_t* ok_sel, uint8_t* ok_con,
+                                 uint8_t* tally_be) {
+  if (!c || !K_be || !qbar_be || (nb && (!cts || !rproof || !cproof || !ok_sel || !ok_con)))
+    return fail(EG_ERR_ARG, "null argument");
+  if (!manifest_ok(nc, spc) || ph >= spc) return fail(EG_ERR_ARG, "bad manifest shape");
+  const ManShape M = uniform_shape(nc, spc, ph, limit);
+  Locked L(c);
+  int rc;
+  if ((rc = use_key_locked(c, K_be))) return rc;
+  return verify_host_locked(c, M, qbar_be, nb, cts, rproof, cproof, cast, ok_sel, ok_con, tally_be);
 }
 
 // ---------------------------------------------------------------------------------
@@ -602,6 +873,49 @@ extern "C" int eg_ctx_set_ct_encrypt(eg_ctx* c, int on) {
   return EG_OK;
 }
 
+// The encryptor's scalar space (32-byte rows): the selection nonces (R, u, cf, vf) x ns, the
+// contest nonces x ncn, the derived (m, sf, sg) x ns, then the nonce sums x ncn.  One element
+// space: the ciphertexts (ns x 2), the selection commitments (ns x 4), the aggregates A, B
+// (ncn x 2), then the contest commitments a, b (ncn x 2).
+struct EncryptLayout {
+  size_t ns, ncn, off_cn, off_der, off_rs, nscal, oCM, oCP, oCC, nU;
+  static constexpr size_t oCT = 0;  // the ciphertexts lead the element space
+  EncryptLayout(const ManShape& M, size_t nb)
+      : ns(nb * M.nsel), ncn(nb * M.nc), off_cn(ns * 4), off_der(off_cn + ncn), off_rs(off_der + ns * 3),
+        nscal(off_rs + ncn), oCM(ns * 2), oCP(oCM + ns * 4), oCC(oCP + ncn * 2), nU(oCC + ncn * 2) {}
+};
+// the selection jobs (a selection job does not know its contest), which:
+//   1  alpha = g^R ; a_real = g^u                -> slot 0
+//   2  beta = K^R g^m ; b_real = K^u             -> slot 1
+//   3  a_fake = g^sf ; b_fake = K^sf g^sg       -> slots 2, 3
+static std::vector<uint32_t> encrypt_sel_jobs(const EncryptLayout& V, int which) {
+  auto J = new_jobs(V.ns);
+  for (size_t i = 0; i < V.ns; ++i) {
+    const uint32_t R = (uint32_t)(i * 4), u = R + 1;
+    const uint32_t dm = (uint32_t)(V.off_der + i * 3), sf = dm + 1, sg = dm + 2;
+    const uint32_t cm = (uint32_t)(V.oCM + i * 4);
+    uint32_t* x = &J[i * kJobWords];
+    if (which == 1) {
+      x[3] = (uint32_t)(V.oCT + i * 2); x[4] = cm; x[5] = R; x[7] = u;
+    } else if (which == 2) {
+      x[3] = (uint32_t)(V.oCT + i * 2 + 1); x[4] = cm + 1; x[5] = R; x[6] = dm; x[7] = u;
+    } else {
+      x[3] = cm + 2; x[4] = cm + 3; x[5] = sf; x[7] = sf; x[8] = sg;
+    }
+  }
+  return J;
+}
+// the contest commitments a = g^u_c ; b = K^u_c (they do not depend on the contests' sizes)
+static std::vector<uint32_t> encrypt_contest_jobs(const EncryptLayout& V) {
+  auto J = new_jobs(V.ncn);
+  for (size_t j = 0; j < V.ncn; ++j) {
+    uint32_t* a = &J[j * kJobWords];
+    a[3] = (uint32_t)(V.oCC + j * 2); a[4] = (uint32_t)(V.oCC + j * 2 + 1);
+    a[5] = (uint32_t)(V.off_cn + j); a[7] = (uint32_t)(V.off_cn + j);
+  }
+  return J;
+}
+
 // One chunk of <= ballot_chunk(nsel) ballots, enqueued on the ctx stream (c->d_qbar already holds
 // Q-bar; the caller holds the lock).  d_votes, the nonces and (when given) the outputs are device
 // pointers; the wire outputs land in output set `set` (two sets, so the caller can copy one
@@ -613,55 +927,37 @@ extern "C" int eg_ctx_set_ct_encrypt(eg_ctx* c, int on) {
 // selections voted 1 with masks.  So they are cached per chunk shape, the host never reads a
 // vote, and with eg_ctx_set_ct_encrypt (k_pow<F, true>, masked scans of 64-entry table columns)
 // neither addresses nor the schedule depend on a nonce or a vote.
-static int encrypt_chunk_locked(eg_ctx* c, size_t nb, size_t nc, size_t spc, const uint8_t* d_votes,
+static int encrypt_chunk_locked(eg_ctx* c, const ManShape& M, size_t nb, const uint8_t* d_votes,
                                 const uint8_t* sel_nonces, const uint8_t* contest_nonces, bool dev_nonces, int set,
                                 const uint8_t** d_cts, const uint8_t** d_rproof, const uint8_t** d_cproof) {
   int rc;
   FbTab G{}, K{};
   if ((rc = enc_tables_locked(c, &G, &K))) return rc;
   const bool ct = c->ct_encrypt != 0;
-  const size_t nsel = nc * spc, ns = nb * nsel, ncn = nb * nc;
-  // scalars: [sel nonces ns*4 (R,u,cf,vf)][contest nonces ncn][derived ns*3 (m,sf,sg)][rsum ncn]
-  const size_t off_cn = ns * 4, off_der = off_cn + ncn, off_rs = off_der + ns * 3, nscal = off_rs + ncn;
+  const EncryptLayout V(M, nb);
+  const size_t ns = V.ns, ncn = V.ncn, oCT = V.oCT, oCM = V.oCM, oCP = V.oCP, oCC = V.oCC, nU = V.nU;
   uint8_t *SC = nullptr, *CH = nullptr, *CHC = nullptr, *d_rp = nullptr, *d_cp = nullptr;
   uint8_t* UBE = nullptr;
   uint32_t* U = nullptr;
-  if ((rc = ws_get(c, W_SCAL, nscal * 32, (void**)&SC))) return rc;
+  if ((rc = ws_get(c, W_SCAL, V.nscal * 32, (void**)&SC))) return rc;
+  if ((rc = ws_get(c, W_E0, nU * kW * 4, (void**)&U))) return rc;
+  ContestTabs T(M);
+  const uint32_t *j1 = nullptr, *j2 = nullptr, *j3 = nullptr, *j4 = nullptr;
+  TableList L;
+  add_contest_tables(L, M, T, false);
+  L.add("1", &j1, [&V]() { return encrypt_sel_jobs(V, 1); });
+  L.add("2", &j2, [&V]() { return encrypt_sel_jobs(V, 2); });
+  L.add("3", &j3, [&V]() { return encrypt_sel_jobs(V, 3); });
+  L.add("4", &j4, [&V]() { return encrypt_contest_jobs(V); });
+  for (size_t ci = 0; ci < M.cls.size(); ++ci) add_class_tables(L, M, T, ci);
+  if ((rc = fetch_tables(c, M.fam + "e/" + std::to_string(nb) + "/" + M.key, L))) return rc;
   const hipMemcpyKind nk = dev_nonces ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   HIPCHK(hipMemcpyAsync(SC, sel_nonces, ns * 128, nk, c->stream));
-  HIPCHK(hipMemcpyAsync(SC + off_cn * 32, contest_nonces, ncn * 32, nk, c->stream));
+  HIPCHK(hipMemcpyAsync(SC + V.off_cn * 32, contest_nonces, ncn * 32, nk, c->stream));
   hipLaunchKernelGGL(k_enc_prep, dim3(tgrid(ns)), dim3(256), 0, c->stream, c->d_q, d_votes, SC, (uint32_t)ns,
-                     SC + off_der * 32, c->resp_plus);
-  hipLaunchKernelGGL(k_enc_rsum, dim3(tgrid(ncn)), dim3(256), 0, c->stream, c->d_q, SC, (uint32_t)ncn, (uint32_t)spc,
-                     SC + off_rs * 32);
+                     SC + V.off_der * 32, c->resp_plus);
+  nonce_sums(c, M, T, SC, ncn, SC + V.off_rs * 32);
   HIPCHK(hipGetLastError());
-  // unified element space: [ciphertexts ns*2][selection commitments ns*4][A,B ncn*2][contest a,b ncn*2]
-  const size_t oCT = 0, oCM = ns * 2, oCP = oCM + ns * 4, oCC = oCP + ncn * 2, nU = oCC + ncn * 2;
-  if ((rc = ws_get(c, W_E0, nU * kW * 4, (void**)&U))) return rc;
-  const std::string key = "e/" + std::to_string(nb) + "/" + std::to_string(nc) + "/" + std::to_string(spc);
-  std::vector<const uint32_t*> jv;
-  rc = cached_job_set(c, key, {"1", "2", "3", "4"}, [&]() {
-    auto J1 = new_jobs(ns), J2 = new_jobs(ns), J3 = new_jobs(ns), J4 = new_jobs(ncn);
-    for (size_t i = 0; i < ns; ++i) {
-      const uint32_t R = (uint32_t)(i * 4), u = R + 1;
-      const uint32_t dm = (uint32_t)(off_der + i * 3), sf = dm + 1, sg = dm + 2;
-      const uint32_t cm = (uint32_t)(oCM + i * 4);
-      uint32_t* a = &J1[i * kJobWords];  // alpha = g^R ; a_real = g^u                -> slot 0
-      a[3] = (uint32_t)(oCT + i * 2); a[4] = cm; a[5] = R; a[7] = u;
-      uint32_t* b = &J2[i * kJobWords];  // beta = K^R g^m ; b_real = K^u             -> slot 1
-      b[3] = (uint32_t)(oCT + i * 2 + 1); b[4] = cm + 1; b[5] = R; b[6] = dm; b[7] = u;
-      uint32_t* d = &J3[i * kJobWords];  // a_fake = g^sf ; b_fake = K^sf g^sg       -> slots 2, 3
-      d[3] = cm + 2; d[4] = cm + 3; d[5] = sf; d[7] = sf; d[8] = sg;
-    }
-    for (size_t j = 0; j < ncn; ++j) {
-      uint32_t* a = &J4[j * kJobWords];  // a = g^u_c ; b = K^u_c
-      a[3] = (uint32_t)(oCC + j * 2); a[4] = (uint32_t)(oCC + j * 2 + 1);
-      a[5] = (uint32_t)(off_cn + j); a[7] = (uint32_t)(off_cn + j);
-    }
-    return std::vector<std::vector<uint32_t>>{std::move(J1), std::move(J2), std::move(J3), std::move(J4)};
-  }, jv);
-  if (rc) return rc;
-  const uint32_t *j1 = jv[0], *j2 = jv[1], *j3 = jv[2], *j4 = jv[3];
   // All four job populations are fixed-base only and independent of each other (j1: alpha and
   // the real-branch a; j2: beta and the real-branch b; j3: the simulated branch; j4: the contest
   // commitments), so they run as two two-part launches whose second part fills the first's
@@ -670,32 +966,30 @@ static int encrypt_chunk_locked(eg_ctx* c, size_t nb, size_t nc, size_t spc, con
   {
     PowShape S{};
     S.nout = 2; S.nfb[0] = 1; S.nfb[1] = 1; S.exp_bytes = 32;
-    PowTail T{};
-    T.S.nout = 2; T.S.nfb[0] = 1; T.S.nfb[1] = 1; T.S.exp_bytes = 32; T.S.tab[1][0] = 1;
-    T.jobs = j4; T.njobs = ncn;
-    if ((rc = launch_pow(c, S, j1, ns, U, SC, U, G, K, nullptr, nullptr, &T, nullptr, ct))) return rc;
+    PowTail TL{};
+    TL.S.nout = 2; TL.S.nfb[0] = 1; TL.S.nfb[1] = 1; TL.S.exp_bytes = 32; TL.S.tab[1][0] = 1;
+    TL.jobs = j4; TL.njobs = ncn;
+    if ((rc = launch_pow(c, S, j1, ns, U, SC, U, G, K, nullptr, nullptr, &TL, nullptr, ct))) return rc;
   }
   {
     PowShape S{};
     S.nout = 2; S.nfb[0] = 2; S.nfb[1] = 1; S.exp_bytes = 32; S.tab[0][0] = 1; S.tab[0][1] = 0; S.tab[1][0] = 1;
     S.fb_small[0][1] = 1;
-    PowTail T{};
-    T.S.nout = 2; T.S.nfb[0] = 1; T.S.nfb[1] = 2; T.S.exp_bytes = 32; T.S.tab[1][0] = 1; T.S.tab[1][1] = 0;
-    T.jobs = j3; T.njobs = ns;
-    if ((rc = launch_pow(c, S, j2, ns, U, SC, U, G, K, nullptr, nullptr, &T, nullptr, ct))) return rc;
+    PowTail TL{};
+    TL.S.nout = 2; TL.S.nfb[0] = 1; TL.S.nfb[1] = 2; TL.S.exp_bytes = 32; TL.S.tab[1][0] = 1; TL.S.tab[1][1] = 0;
+    TL.jobs = j3; TL.njobs = ns;
+    if ((rc = launch_pow(c, S, j2, ns, U, SC, U, G, K, nullptr, nullptr, &TL, nullptr, ct))) return rc;
   }
   hipLaunchKernelGGL(k_enc_order, dim3(tgrid(ns * (2 * kW / 4))), dim3(256), 0, c->stream, U + oCM * kW, d_votes,
                      (uint32_t)ns);
   HIPCHK(hipGetLastError());
-  if ((rc = run_prod(c, U + oCT * kW, GroupMap{2, (uint32_t)nc, 1, (uint32_t)(2 * spc), (uint32_t)(2 * nsel)},
-                     ncn * 2, spc, 2, U + oCP * kW)))
-    return rc;
+  if ((rc = contest_aggregates(c, M, T, nb, U + oCT * kW, U + oCP * kW))) return rc;
   uint8_t* const want_cts = const_cast<uint8_t*>(*d_cts);
   uint8_t* const want_rp = const_cast<uint8_t*>(*d_rproof);
   uint8_t* const want_cp = const_cast<uint8_t*>(*d_cproof);
   if ((rc = ws_get(c, set ? W_EB0 : W_BE0, nU * 512, (void**)&UBE))) return rc;
   if (want_cts) {  // the ciphertexts (elements [oCT, oCM)) straight into the caller's buffer
-    static_assert(oCT == 0, "ciphertexts lead the element space");
+    static_assert(EncryptLayout::oCT == 0, "ciphertexts lead the element space");
     if ((rc = launch_export(c, U, oCM, want_cts))) return rc;
     if ((rc = launch_export(c, U + oCM * kW, nU - oCM, UBE + oCM * 512))) return rc;
   } else {
@@ -721,14 +1015,14 @@ static int encrypt_chunk_locked(eg_ctx* c, size_t nb, size_t nc, size_t spc, con
     return rc;
   if (want_rp) d_rp = want_rp;
   else if ((rc = ws_get(c, set ? W_EB1 : W_FLAGS, ns * 128, (void**)&d_rp))) return rc;
-  // set 0's contest proofs get their own slot: W_TMP is run_prod's scratch, and the next chunk's
-  // run_prod may run while this chunk's proofs are still being copied back (ADVICE r01)
+  // set 0's contest proofs get their own slot: W_TMP is the product tree's scratch, and the next
+  // chunk's products may run while this chunk's proofs are still being copied back (ADVICE r01)
   if (want_cp) d_cp = want_cp;
   else if ((rc = ws_get(c, set ? W_EB2 : W_EA2, ncn * 64 + 64, (void**)&d_cp))) return rc;
   hipLaunchKernelGGL(k_enc_finish, dim3(tgrid(ns)), dim3(256), 0, c->stream, c->d_q, d_votes, SC, CH, (uint32_t)ns,
                      d_rp, c->resp_plus);
-  hipLaunchKernelGGL(k_response, dim3(tgrid(ncn)), dim3(256), 0, c->stream, c->d_q, SC + off_cn * 32, CHC,
-                     SC + off_rs * 32, 32u, (uint32_t)ncn, d_cp, c->resp_plus);
+  hipLaunchKernelGGL(k_response, dim3(tgrid(ncn)), dim3(256), 0, c->stream, c->d_q, SC + V.off_cn * 32, CHC,
+                     SC + V.off_rs * 32, 32u, (uint32_t)ncn, d_cp, c->resp_plus);
   HIPCHK(hipGetLastError());
   *d_cts = CT_BE;
   *d_rproof = d_rp;
@@ -739,24 +1033,18 @@ static int encrypt_chunk_locked(eg_ctx* c, size_t nb, size_t nc, size_t spc, con
 // Ballots are encrypted in the verifier's chunks (ballot_chunk: 16,384 ballots for the configs'
 // manifests): the device working set is ~184 KB per 4x(5+1) ballot, so a 1M-ballot batch
 // (configs[2]) runs in 1.7 GB chunks instead of one ~180 GB element space.  Output is
-// independent of the chunking (nonces injected).
-
-extern "C" int eg_encrypt_ballots(eg_ctx* c, const uint8_t K_be[512], const uint8_t qbar_be[32], size_t nb, size_t nc,
-                                  size_t spc, const uint8_t* votes, const uint8_t* sel_nonces,
-                                  const uint8_t* contest_nonces, uint8_t* cts, uint8_t* rproof, uint8_t* cproof) {
-  if (!c || !K_be || !qbar_be || (nb && (!votes || !sel_nonces || !contest_nonces || !cts || !rproof || !cproof)))
-    return fail(EG_ERR_ARG, "null argument");
-  if (!nb) return EG_OK;
-  if (!manifest_ok(nc, spc)) return fail(EG_ERR_ARG, "bad manifest shape");
-  Locked L(c);
+// independent of the chunking (nonces injected).  Both drivers run under the caller's lock,
+// after its argument checks and use_key_locked.
+// Host pointers, a software pipeline: chunk k computes on the ctx stream while chunk k-1's
+// outputs go back on the copy stream (two output sets; a pageable D2H blocks the host, so it is
+// issued only after chunk k is enqueued).  The votes go up once for the whole batch.
+static int encrypt_host_locked(eg_ctx* c, const ManShape& M, const uint8_t* qbar_be, size_t nb, const uint8_t* votes,
+                               const uint8_t* sel_nonces, const uint8_t* contest_nonces, uint8_t* cts,
+                               uint8_t* rproof, uint8_t* cproof) {
   int rc;
-  if ((rc = use_key_locked(c, K_be))) return rc;
   HIPCHK(hipMemcpyAsync(c->d_qbar, qbar_be, 32, hipMemcpyHostToDevice, c->stream));
   if ((rc = ensure_copy_stream(c))) return rc;
-  // Software pipeline: chunk k computes on the ctx stream while chunk k-1's outputs go back on
-  // the copy stream (two output sets; a pageable D2H blocks the host, so it is issued only
-  // after chunk k is enqueued).  The votes go up once for the whole batch.
-  const size_t nsel = nc * spc, chunk = host_chunk(nb, nsel);
+  const size_t nc = M.nc, nsel = M.nsel, chunk = host_chunk(nb, nsel);
   uint8_t* d_votes = nullptr;
   if ((rc = upload(c, W_H0, votes, nb * nsel, (void**)&d_votes))) return rc;
   struct Out { size_t b0, n; const uint8_t *cts, *rp, *cp; } prev{};
@@ -774,7 +1062,7 @@ extern "C" int eg_encrypt_ballots(eg_ctx* c, const uint8_t K_be[512], const uint
     const int set = (int)(k & 1);
     if (k >= 2) HIPCHK(hipStreamWaitEvent(c->stream, c->up_ev[set], 0));  // chunk k-2's outputs are home
     Out cur{b0, n, nullptr, nullptr, nullptr};
-    if ((rc = encrypt_chunk_locked(c, n, nc, spc, d_votes + b0 * nsel, sel_nonces + b0 * nsel * 128,
+    if ((rc = encrypt_chunk_locked(c, M, n, d_votes + b0 * nsel, sel_nonces + b0 * nsel * 128,
                                    contest_nonces + b0 * nc * 32, false, set, &cur.cts, &cur.rp, &cur.cp)))
       break;
     HIPCHK(hipEventRecord(c->done_ev[set], c->stream));
@@ -787,6 +1075,40 @@ extern "C" int eg_encrypt_ballots(eg_ctx* c, const uint8_t K_be[512], const uint
   return rc;
 }
 
+// device pointers in and out: the kernels write the caller's device buffers directly
+static int encrypt_dev_locked(eg_ctx* c, const ManShape& M, const uint8_t* qbar_be, size_t nb, const uint8_t* d_votes,
+                              const uint8_t* d_sel_nonces, const uint8_t* d_contest_nonces, uint8_t* d_cts,
+                              uint8_t* d_rproof, uint8_t* d_cproof) {
+  int rc;
+  const size_t nc = M.nc, nsel = M.nsel, chunk = ballot_chunk(nsel);
+  HIPCHK(hipMemcpyAsync(c->d_qbar, qbar_be, 32, hipMemcpyHostToDevice, c->stream));
+  size_t k = 0;
+  for (size_t b0 = 0; b0 < nb; b0 += chunk, ++k) {
+    const size_t n = std::min(chunk, nb - b0);
+    const uint8_t *o_cts = d_cts + b0 * nsel * 1024, *o_rp = d_rproof + b0 * nsel * 128,
+                  *o_cp = d_cproof + b0 * nc * 64;
+    if ((rc = encrypt_chunk_locked(c, M, n, d_votes + b0 * nsel, d_sel_nonces + b0 * nsel * 128,
+                                   d_contest_nonces + b0 * nc * 32, true, (int)(k & 1), &o_cts, &o_rp, &o_cp)))
+      return rc;
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return EG_OK;
+}
+
+extern "C" int eg_encrypt_ballots(eg_ctx* c, const uint8_t K_be[512], const uint8_t qbar_be[32], size_t nb, size_t nc,
+                                  size_t spc, const uint8_t* votes, const uint8_t* sel_nonces,
+                                  const uint8_t* contest_nonces, uint8_t* cts, uint8_t* rproof, uint8_t* cproof) {
+  if (!c || !K_be || !qbar_be || (nb && (!votes || !sel_nonces || !contest_nonces || !cts || !rproof || !cproof)))
+    return fail(EG_ERR_ARG, "null argument");
+  if (!nb) return EG_OK;
+  if (!manifest_ok(nc, spc)) return fail(EG_ERR_ARG, "bad manifest shape");
+  const ManShape M = uniform_shape(nc, spc, 0, 0);
+  Locked L(c);
+  int rc;
+  if ((rc = use_key_locked(c, K_be))) return rc;
+  return encrypt_host_locked(c, M, qbar_be, nb, votes, sel_nonces, contest_nonces, cts, rproof, cproof);
+}
+
 extern "C" int eg_encrypt_ballots_dev(eg_ctx* c, const uint8_t K_be[512], const uint8_t qbar_be[32], size_t nb,
                                       size_t nc, size_t spc, const uint8_t* d_votes, const uint8_t* d_sel_nonces,
                                       const uint8_t* d_contest_nonces, uint8_t* d_cts, uint8_t* d_rproof,
@@ -796,23 +1118,11 @@ extern "C" int eg_encrypt_ballots_dev(eg_ctx* c, const uint8_t K_be[512], const 
     return fail(EG_ERR_ARG, "null argument");
   if (!nb) return EG_OK;
   if (!manifest_ok(nc, spc)) return fail(EG_ERR_ARG, "bad manifest shape");
+  const ManShape M = uniform_shape(nc, spc, 0, 0);
   Locked L(c);
   int rc;
   if ((rc = use_key_locked(c, K_be))) return rc;
-  const size_t nsel = nc * spc, chunk = ballot_chunk(nsel);
-  HIPCHK(hipMemcpyAsync(c->d_qbar, qbar_be, 32, hipMemcpyHostToDevice, c->stream));
-  size_t k = 0;
-  for (size_t b0 = 0; b0 < nb; b0 += chunk, ++k) {
-    const size_t n = std::min(chunk, nb - b0);
-    // the kernels write the caller's device buffers directly
-    const uint8_t *o_cts = d_cts + b0 * nsel * 1024, *o_rp = d_rproof + b0 * nsel * 128,
-                  *o_cp = d_cproof + b0 * nc * 64;
-    if ((rc = encrypt_chunk_locked(c, n, nc, spc, d_votes + b0 * nsel, d_sel_nonces + b0 * nsel * 128,
-                                   d_contest_nonces + b0 * nc * 32, true, (int)(k & 1), &o_cts, &o_rp, &o_cp)))
-      return rc;
-  }
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return EG_OK;
+  return encrypt_dev_locked(c, M, qbar_be, nb, d_votes, d_sel_nonces, d_contest_nonces, d_cts, d_rproof, d_cproof);
 }
 
 // ---------------------------------------------------------------------------------

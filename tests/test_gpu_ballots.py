@@ -169,3 +169,46 @@ def test_window_path_context_matches_comb(group, monkeypatch):
             assert be2i(Ma[i]) == pow(be2i(texts[i, 0]), secret, og.p)
     finally:
         g2.close()
+
+
+def test_window_path_context_with_a_split_beta_launch(group, monkeypatch):
+    """An EG_NO_COMB=1 context keeps no comb powers of the selections (the gathered contest jobs
+    run the 4-bit window), so the beta jobs launch 2 keeps after the beta head must not be
+    handed a place to store theirs.  Manifest(4, 5, 1) x 4 ballots is 96 selection jobs = 3
+    workgroups of 32; EG_POW_SLOTS=2 puts one workgroup of betas (ballot 0 and a third of
+    ballot 1) into launch 1 and leaves 64 for launch 2.  Verdicts and tally must equal the
+    default context's and the CPython product, and a tamper on either side of the split must
+    fail exactly its selection."""
+    from electionguard.ballot import (ElectionKey, EncryptedBallots, Manifest, Verifier, batch_encryption,
+                                      random_scalars, random_votes)
+    from electionguard.core import GroupContext
+    og, rng, K, qbar, key = _setup(group, seed=43)
+    man = Manifest(4, 5, 1)
+    nb = 4
+    assert nb * man.nsel == 96
+    nr = np.random.default_rng(43)
+    eb = batch_encryption(group, key, qbar, man, random_votes(nr, man, nb),
+                          random_scalars(nr, (nb, man.nsel, 4), og.q), random_scalars(nr, (nb, man.n_contests), og.q))
+    monkeypatch.setenv("EG_NO_COMB", "1")
+    g2 = GroupContext(group.p, group.q, group.g, device=group.device)
+    monkeypatch.delenv("EG_NO_COMB")
+    try:
+        key2 = ElectionKey(g2, K)
+        monkeypatch.setenv("EG_POW_SLOTS", "2")
+        s1, c1, t1 = Verifier(group, key, qbar, man).verify(eb)
+        s2, c2, t2 = Verifier(g2, key2, qbar, man).verify(eb)
+        assert s1.all() and c1.all() and (s2 == s1).all() and (c2 == c1).all() and (t2 == t1).all()
+        for i, s in enumerate(man.real_index.tolist()):
+            for comp in range(2):
+                acc = 1
+                for b in range(nb):
+                    acc = acc * be2i(eb.cts[b, s, comp]) % og.p
+                assert be2i(t2[i, comp]) == acc, (i, comp)
+        rp = eb.rproof.copy()
+        rp[0, 5, 3, 11] ^= 0x04   # a beta-head job (launch 1)
+        rp[3, 17, 1, 20] ^= 0x02  # job 89: a beta job of launch 2
+        for g, k in ((group, key), (g2, key2)):
+            s3, c3, _ = Verifier(g, k, qbar, man).verify(EncryptedBallots(eb.cts, rp, eb.cproof), with_tally=False)
+            assert np.argwhere(~s3).tolist() == [[0, 5], [3, 17]] and c3.all()
+    finally:
+        g2.close()

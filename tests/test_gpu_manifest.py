@@ -427,3 +427,38 @@ def test_argument_validation(group, election, oracle_m):
         # the context is still usable
         ok_s, ok_c, _ = V.verify(EncryptedBallots(cts, rp, cp), with_tally=False)
         assert ok_s.all() and ok_c.all(), what
+
+
+# ---------------------------------------------------------------------------------------------
+# the k_pow launch plan of the table-addressed path
+# ---------------------------------------------------------------------------------------------
+def test_launch_split_independent_table_path(group, election, monkeypatch):
+    """The table-addressed verifier shares the uniform one's beta head (the first betas ride in
+    launch 1 to fill its last round of resident workgroups).  Three classes, nsel = 15, 12
+    ballots: 180 selection jobs = 6 workgroups; EG_POW_SLOTS = 0 (no head), 4 (a head of 64
+    jobs) and 5 (128) move the split.  Verdicts and tally must not depend on it, against the
+    CPython product and a tamper on each side of the contest layer."""
+    from electionguard.ballot import ElectionManifest, EncryptedBallots, Verifier
+    _, _, qbar, key = election
+    man = ElectionManifest([(2, 1), (7, 3), (1, 1)])
+    assert man.nsel == 15 and len(set(man.spc_list.tolist())) == 3
+    nb = 12
+    _, _, _, eb = _gpu_ballots(group, key, qbar, man, nb, 23)
+    want = _py_tally(eb.cts, man.real_index.tolist())
+    rp, cp = eb.rproof.copy(), eb.cproof.copy()
+    rp[0, 4, 2, 6] ^= 0x10     # a selection of ballot 0 (a beta-head job when split)
+    cp[11, 1, 1, 8] ^= 0x01    # the 10-selection contest of the last ballot
+    V = Verifier(group, key, qbar, man)
+    base = None
+    for slots in ("0", "4", "5"):
+        monkeypatch.setenv("EG_POW_SLOTS", slots)
+        ok_s, ok_c, tally = V.verify(eb)
+        assert ok_s.all() and ok_c.all(), slots
+        assert np.array_equal(tally, want), slots
+        if base is None:
+            base = (ok_s, ok_c, tally)
+        assert all(np.array_equal(x, y) for x, y in zip((ok_s, ok_c, tally), base)), slots
+        ok_s, ok_c, _ = V.verify(EncryptedBallots(eb.cts, rp, eb.cproof), with_tally=False)
+        assert np.argwhere(~ok_s).tolist() == [[0, 4]] and ok_c.all(), slots
+        ok_s, ok_c, _ = V.verify(EncryptedBallots(eb.cts, eb.rproof, cp), with_tally=False)
+        assert ok_s.all() and np.argwhere(~ok_c).tolist() == [[11, 1]], slots
