@@ -40,6 +40,7 @@
 #include "eg_range.hpp"
 #include "eg_preencrypt.hpp"
 #include "eg_pow16.h"
+#include "eg_stage.hpp"
 
 using namespace eg;
 
@@ -168,7 +169,7 @@ constexpr int kCtEncWindow = 6;
 
 enum Slot {
   W_IN0, W_IN1, W_EXP, W_OUT, W_E0, W_E1, W_E2, W_E3, W_JOBS, W_SCR, W_TMP, W_FLAGS, W_SCAL,
-  W_BE0, W_BE1, W_BE2, W_OK0, W_OK1, W_OFF, W_H0, W_H1, W_H2, W_H3, W_H4, W_H5, W_H6, W_H7, W_H8, W_EB0, W_EB1, W_EB2, W_EA2, W_YA, W_YB, W_RZ, W_CRF, W_CAST, W_ANY, W_GATHER, W_KBE, W_NSLOT
+  W_BE0, W_BE1, W_BE2, W_OK0, W_OK1, W_OFF, W_H0, W_H1, W_H2, W_H3, W_H4, W_H5, W_H6, W_H7, W_H8, W_EB0, W_EB1, W_EB2, W_EA2, W_YA, W_YB, W_RZ, W_CRF, W_CAST, W_ANY, W_GATHER, W_KBE, W_STAGE, W_NSLOT
 };
 
 struct eg_ctx {
@@ -288,6 +289,37 @@ static int ws_get(eg_ctx* c, Slot s, size_t bytes, void** out) {
 
 static inline unsigned grid_for(size_t groups) { return (unsigned)((groups + kGroupsPerBlock - 1) / kGroupsPerBlock); }
 static inline size_t padded_groups(size_t groups) { return (size_t)grid_for(groups) * kGroupsPerBlock; }
+// grid of a one-thread-per-item launch of 256-thread blocks (kBlock is 256 too)
+static inline unsigned cgrid(size_t n) { return (unsigned)((n + 255) / 256); }
+
+static bool aligned16(std::initializer_list<const void*> ps) {
+  for (const void* p : ps)
+    if ((uintptr_t)p & 15) return false;
+  return true;
+}
+
+// eg_stage.hpp's operations on the ctx stream (the caller holds the lock).  Host-mode columns live
+// in W_STAGE and nowhere else, so no staging buffer can share a slot with the workspace of the
+// chunk function it feeds.
+struct StreamOps {
+  eg_ctx* c;
+  int alloc(size_t bytes, void** out) const { return ws_get(c, W_STAGE, bytes, out); }
+  int h2d(void* dst, const void* src, size_t bytes) const {
+    HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
+    return EG_OK;
+  }
+  int d2h(void* dst, const void* src, size_t bytes) const {
+    HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+    return EG_OK;
+  }
+  int sync() const {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return EG_OK;
+  }
+};
+struct Stage : egstage::Stage<StreamOps> {
+  Stage(eg_ctx* c, bool host, size_t n, size_t chunk) : egstage::Stage<StreamOps>(StreamOps{c}, host, n, chunk) {}
+};
 
 // ---- launch wrappers (ctx stream) ----
 static int launch_import(eg_ctx* c, const uint8_t* d_be, size_t n, uint32_t* d_out, uint8_t* d_ltp) {

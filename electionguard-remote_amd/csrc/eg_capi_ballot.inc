@@ -16,8 +16,6 @@
 // arithmetic addressing, the benchmark's kernels and plan) from a table-addressed one (the
 // entry points of eg_capi_manifest.inc: per-contest device tables).
 
-static inline unsigned tgrid(size_t n) { return (unsigned)((n + 255) / 256); }
-
 // One device copy of a host job table (freed again when the upload fails).  EG_TEST_FAIL_JOBS=k
 // (read at context creation, tests only) makes the k-th upload of the context fail as an
 // out-of-memory hipMalloc would.
@@ -118,7 +116,7 @@ static int launch_hash(eg_ctx* c, uint32_t n, std::vector<HashSrc> src, const ui
   if (!n) return EG_OK;
   if (src.size() > 8) return fail(EG_ERR_ARG, "more than 8 hash elements");
   while (src.size() < 8) src.push_back(HashSrc{nullptr, 0, 0});
-  hipLaunchKernelGGL(k_hash_check, dim3(tgrid(n)), dim3(256), 0, c->stream, c->d_q, c->d_qbar, n,
+  hipLaunchKernelGGL(k_hash_check, dim3(cgrid(n)), dim3(256), 0, c->stream, c->d_q, c->d_qbar, n,
                      (uint32_t)(std::count_if(src.begin(), src.end(), [](const HashSrc& h) { return h.ptr != nullptr; })),
                      src[0], src[1], src[2], src[3], src[4], src[5], src[6], src[7], proofs, pw, ci0, ci1, pre_ok,
                      pre_ok2, pre2_div, ok, out_h, c->hash_fmt);
@@ -361,29 +359,29 @@ static int contest_aggregates(eg_ctx* c, const ManShape& M, const ContestTabs& T
 static void contest_scalars(eg_ctx* c, const ManShape& M, const ContestTabs& T, uint8_t* sc, size_t ncn, uint8_t* negL,
                             uint8_t* okc) {
   if (M.uniform)
-    hipLaunchKernelGGL(k_scalar_prep, dim3(tgrid(ncn)), dim3(256), 0, c->stream, c->d_q, sc, (uint32_t)ncn, 2u, 0u,
+    hipLaunchKernelGGL(k_scalar_prep, dim3(cgrid(ncn)), dim3(256), 0, c->stream, c->d_q, sc, (uint32_t)ncn, 2u, 0u,
                        M.ulimit, negL, okc, c->resp_plus, 0x1u);
   else
-    hipLaunchKernelGGL(k_scalar_prep_tab, dim3(tgrid(ncn)), dim3(256), 0, c->stream, c->d_q, sc, (uint32_t)ncn, 2u, 0u,
+    hipLaunchKernelGGL(k_scalar_prep_tab, dim3(cgrid(ncn)), dim3(256), 0, c->stream, c->d_q, sc, (uint32_t)ncn, 2u, 0u,
                        T.limit, (uint32_t)M.nc, negL, okc, c->resp_plus, 0x1u);
 }
 // (A, B) flags per contest: the AND of its selections' range + residue flags
 static void contest_flags(eg_ctx* c, const ManShape& M, const ContestTabs& T, const uint8_t* ltp, size_t ncn,
                           uint8_t* crf) {
   if (M.uniform)
-    hipLaunchKernelGGL(k_contest_flags, dim3(tgrid(ncn * 2)), dim3(256), 0, c->stream, ltp, (uint32_t)ncn, M.uspc,
+    hipLaunchKernelGGL(k_contest_flags, dim3(cgrid(ncn * 2)), dim3(256), 0, c->stream, ltp, (uint32_t)ncn, M.uspc,
                        crf);
   else
-    hipLaunchKernelGGL(k_contest_flags_seg, dim3(tgrid(ncn * 2)), dim3(256), 0, c->stream, ltp, (uint32_t)ncn,
+    hipLaunchKernelGGL(k_contest_flags_seg, dim3(cgrid(ncn * 2)), dim3(256), 0, c->stream, ltp, (uint32_t)ncn,
                        (uint32_t)M.nc, (uint32_t)M.nsel, T.first, T.spc, crf);
 }
 // the sum of each contest's selection nonces R (the encryptor's scalars sc) -> rsum
 static void nonce_sums(eg_ctx* c, const ManShape& M, const ContestTabs& T, const uint8_t* sc, size_t ncn,
                        uint8_t* rsum) {
   if (M.uniform)
-    hipLaunchKernelGGL(k_enc_rsum, dim3(tgrid(ncn)), dim3(256), 0, c->stream, c->d_q, sc, (uint32_t)ncn, M.uspc, rsum);
+    hipLaunchKernelGGL(k_enc_rsum, dim3(cgrid(ncn)), dim3(256), 0, c->stream, c->d_q, sc, (uint32_t)ncn, M.uspc, rsum);
   else
-    hipLaunchKernelGGL(k_enc_rsum_seg, dim3(tgrid(ncn)), dim3(256), 0, c->stream, c->d_q, sc, (uint32_t)ncn,
+    hipLaunchKernelGGL(k_enc_rsum_seg, dim3(cgrid(ncn)), dim3(256), 0, c->stream, c->d_q, sc, (uint32_t)ncn,
                        (uint32_t)M.nc, (uint32_t)M.nsel, T.first, T.spc, rsum);
 }
 // products over the nbc ballots with cast[b] != 0 (all: cast == nullptr) of every real
@@ -586,7 +584,7 @@ static int verify_chunk_locked(eg_ctx* c, const ManShape& M, size_t nbc, const u
   HIPCHK(hipMemcpyAsync(SC, d_rproof, ns * 128, hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(SC + V.off_c * 32, d_cproof, ncn * 64, hipMemcpyDeviceToDevice, c->stream));
   // plus convention: c0, c1 and c negated in place (the comb exponents), the g terms take +c1, +L c
-  hipLaunchKernelGGL(k_scalar_prep, dim3(tgrid(ns)), dim3(256), 0, c->stream, c->d_q, SC, (uint32_t)ns, 4u, 2u, 1u,
+  hipLaunchKernelGGL(k_scalar_prep, dim3(cgrid(ns)), dim3(256), 0, c->stream, c->d_q, SC, (uint32_t)ns, 4u, 2u, 1u,
                      SC + V.off_neg * 32, OKR, c->resp_plus, 0x5u);
   contest_scalars(c, M, T, SC + V.off_c * 32, ncn, SC + V.off_negL * 32, OKC);
   HIPCHK(hipGetLastError());
@@ -954,7 +952,7 @@ static int encrypt_chunk_locked(eg_ctx* c, const ManShape& M, size_t nb, const u
   const hipMemcpyKind nk = dev_nonces ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   HIPCHK(hipMemcpyAsync(SC, sel_nonces, ns * 128, nk, c->stream));
   HIPCHK(hipMemcpyAsync(SC + V.off_cn * 32, contest_nonces, ncn * 32, nk, c->stream));
-  hipLaunchKernelGGL(k_enc_prep, dim3(tgrid(ns)), dim3(256), 0, c->stream, c->d_q, d_votes, SC, (uint32_t)ns,
+  hipLaunchKernelGGL(k_enc_prep, dim3(cgrid(ns)), dim3(256), 0, c->stream, c->d_q, d_votes, SC, (uint32_t)ns,
                      SC + V.off_der * 32, c->resp_plus);
   nonce_sums(c, M, T, SC, ncn, SC + V.off_rs * 32);
   HIPCHK(hipGetLastError());
@@ -980,7 +978,7 @@ static int encrypt_chunk_locked(eg_ctx* c, const ManShape& M, size_t nb, const u
     TL.jobs = j3; TL.njobs = ns;
     if ((rc = launch_pow(c, S, j2, ns, U, SC, U, G, K, nullptr, nullptr, &TL, nullptr, ct))) return rc;
   }
-  hipLaunchKernelGGL(k_enc_order, dim3(tgrid(ns * (2 * kW / 4))), dim3(256), 0, c->stream, U + oCM * kW, d_votes,
+  hipLaunchKernelGGL(k_enc_order, dim3(cgrid(ns * (2 * kW / 4))), dim3(256), 0, c->stream, U + oCM * kW, d_votes,
                      (uint32_t)ns);
   HIPCHK(hipGetLastError());
   if ((rc = contest_aggregates(c, M, T, nb, U + oCT * kW, U + oCP * kW))) return rc;
@@ -1019,9 +1017,9 @@ static int encrypt_chunk_locked(eg_ctx* c, const ManShape& M, size_t nb, const u
   // chunk's products may run while this chunk's proofs are still being copied back (ADVICE r01)
   if (want_cp) d_cp = want_cp;
   else if ((rc = ws_get(c, set ? W_EB2 : W_EA2, ncn * 64 + 64, (void**)&d_cp))) return rc;
-  hipLaunchKernelGGL(k_enc_finish, dim3(tgrid(ns)), dim3(256), 0, c->stream, c->d_q, d_votes, SC, CH, (uint32_t)ns,
+  hipLaunchKernelGGL(k_enc_finish, dim3(cgrid(ns)), dim3(256), 0, c->stream, c->d_q, d_votes, SC, CH, (uint32_t)ns,
                      d_rp, c->resp_plus);
-  hipLaunchKernelGGL(k_response, dim3(tgrid(ncn)), dim3(256), 0, c->stream, c->d_q, SC + V.off_cn * 32, CHC,
+  hipLaunchKernelGGL(k_response, dim3(cgrid(ncn)), dim3(256), 0, c->stream, c->d_q, SC + V.off_cn * 32, CHC,
                      SC + V.off_rs * 32, 32u, (uint32_t)ncn, d_cp, c->resp_plus);
   HIPCHK(hipGetLastError());
   *d_cts = CT_BE;
@@ -1239,7 +1237,7 @@ extern "C" int eg_trustee_decrypt_batch(eg_ctx* c, const uint8_t secret_be[32], 
                         nullptr, 0, 0, kNone, nullptr, nullptr, 0, nullptr, CH)))
     return rc;
   if ((rc = ws_get(c, W_OK1, n * 64, (void**)&PR))) return rc;
-  hipLaunchKernelGGL(k_response, dim3(tgrid(n)), dim3(256), 0, c->stream, c->d_q, SC + 32, CH, SC, 0u, (uint32_t)n, PR,
+  hipLaunchKernelGGL(k_response, dim3(cgrid(n)), dim3(256), 0, c->stream, c->d_q, SC + 32, CH, SC, 0u, (uint32_t)n, PR,
                      c->resp_plus);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpy2DAsync(out_M, 512, OBE, 1536, 512, n, hipMemcpyDeviceToHost, c->stream));
@@ -1297,7 +1295,7 @@ extern "C" int eg_verify_shares(eg_ctx* c, const uint8_t qbar_be[32], const uint
   if ((rc = launch_import(c, IN, n * 4, E, nullptr))) return rc;
   if ((rc = ws_get(c, W_OK0, n, (void**)&OKR))) return rc;
   NEG = SC + n * 64;
-  hipLaunchKernelGGL(k_scalar_prep, dim3(tgrid(n)), dim3(256), 0, c->stream, c->d_q, SC, (uint32_t)n, 2u, 0u, 1u,
+  hipLaunchKernelGGL(k_scalar_prep, dim3(cgrid(n)), dim3(256), 0, c->stream, c->d_q, SC, (uint32_t)n, 2u, 0u, 1u,
                      NEG, OKR, 0u, 0u);
   HIPCHK(hipGetLastError());
   if ((rc = ws_get(c, W_E1, n * 4 * kW * 4, (void**)&O))) return rc;

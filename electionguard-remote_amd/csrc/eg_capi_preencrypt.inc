@@ -1,8 +1,9 @@
 // eg_capi_preencrypt.inc — pre-encrypted ballots (include/eg_hip_preencrypt.h; included by
 // eg_capi.hip after eg_capi_range.inc: the shape checks, table cache, key and launch helpers are
-// eg_capi_ballot.inc's and eg_capi_manifest.inc's, cgrid / aligned16 / derive_locked
-// eg_capi_codes.inc's).  Kernels: eg_preencrypt.hpp, k_seg_hash and k_derive_nonces of
-// eg_codes.hpp, and for every group operation the existing k_pow / k_prod_tab / import / export.
+// eg_capi_ballot.inc's and eg_capi_manifest.inc's, derive_locked eg_capi_codes.inc's).  Kernels:
+// eg_preencrypt.hpp, k_seg_hash and k_derive_nonces of eg_codes.hpp, and for every group operation
+// the existing k_pow / k_prod_tab / import / export.  Each of the three entry points and its _dev
+// twin are one body taking `bool host`, around one staged run (eg_stage.hpp) of the chunk function.
 //
 // A component is one fixed-base job of the encryptor's kind, (alpha, beta) = (g^rho, K^rho g^d)
 // with d = [i = j] a one-window term (PowShape.fb_small, as the vote m of beta = K^R g^m), on the
@@ -173,79 +174,53 @@ static int pre_chunk_locked(eg_ctx* c, const PreShape& P, size_t nbc, uint32_t c
   return pre_conf_hashes(c, P, nbc, d_dcon, d_mh, d_ids, d_sorted, tv[4], tv[5], d_chash, d_conf);
 }
 
+// in host mode the device holds one chunk however many ballots come in
+static int preencrypt_ballots(eg_ctx* c, bool host, const uint8_t* K_be, size_t nb, size_t nc, const uint32_t* spc,
+                              uint32_t cb, const uint8_t* dcon, const uint8_t* mh, const uint8_t* ids,
+                              const uint8_t* bn, uint8_t* sorted, uint32_t* perm, uint32_t* codes, uint8_t* unique,
+                              uint8_t* conf, uint8_t* chash, uint8_t* vec) {
+  int rc;
+  if ((rc = pre_check(c, nc, spc, nullptr, false, cb,
+                      K_be && (!nb || (dcon && mh && ids && bn && sorted && perm && codes && unique && conf)))))
+    return rc;
+  if (!host && !aligned16({dcon, mh, ids, bn, sorted, conf, chash, vec}))
+    return pre_fail("device pointer not 16-byte aligned");
+  if (!nb) return EG_OK;
+  const PreShape P = pre_shape(nc, spc, nullptr);
+  const size_t nsel = P.M.nsel;
+  Locked L(c);
+  if ((rc = use_key_locked(c, K_be))) return rc;
+  Stage st(c, host, nb, pre_chunk(P.V));
+  st.once(dcon, nc * 32);
+  st.once(mh, 32);
+  st.in(ids, 32);
+  st.in(bn, 32);
+  st.out(sorted, nsel * 32);
+  st.out(perm, nsel * 4);
+  st.out(codes, nsel * 4);
+  st.out(unique, 1);
+  st.out(conf, 32);
+  st.out(chash, nc * 32);
+  st.out(vec, P.V * 1024);
+  return st.run([&](size_t n) {
+    return pre_chunk_locked(c, P, n, cb, dcon, mh, ids, bn, sorted, perm, codes, unique, conf, chash, vec);
+  });
+}
+
 extern "C" int eg_preencrypt_ballots_dev(eg_ctx* c, const uint8_t K_be[512], size_t nb, size_t nc, const uint32_t* spc,
                                          uint32_t cb, const uint8_t* d_dcon, const uint8_t* d_mh, const uint8_t* d_ids,
                                          const uint8_t* d_bn, uint8_t* d_sorted, uint32_t* d_perm, uint32_t* d_codes,
                                          uint8_t* d_unique, uint8_t* d_conf, uint8_t* d_chash, uint8_t* d_vec) {
-  int rc;
-  if ((rc = pre_check(c, nc, spc, nullptr, false, cb,
-                      K_be && (!nb || (d_dcon && d_mh && d_ids && d_bn && d_sorted && d_perm && d_codes && d_unique &&
-                                       d_conf)))))
-    return rc;
-  if (!aligned16({d_dcon, d_mh, d_ids, d_bn, d_sorted, d_conf, d_chash, d_vec}))
-    return pre_fail("device pointer not 16-byte aligned");
-  if (!nb) return EG_OK;
-  const PreShape P = pre_shape(nc, spc, nullptr);
-  const size_t nsel = P.M.nsel, chunk = pre_chunk(P.V);
-  Locked L(c);
-  if ((rc = use_key_locked(c, K_be))) return rc;
-  for (size_t b0 = 0; b0 < nb; b0 += chunk) {
-    const size_t n = std::min(chunk, nb - b0);
-    if ((rc = pre_chunk_locked(c, P, n, cb, d_dcon, d_mh, d_ids + b0 * 32, d_bn + b0 * 32, d_sorted + b0 * nsel * 32,
-                               d_perm + b0 * nsel, d_codes + b0 * nsel, d_unique + b0, d_conf + b0 * 32,
-                               d_chash ? d_chash + b0 * nc * 32 : nullptr,
-                               d_vec ? d_vec + b0 * P.V * 1024 : nullptr)))
-      return rc;
-  }
-  return EG_OK;
+  return preencrypt_ballots(c, false, K_be, nb, nc, spc, cb, d_dcon, d_mh, d_ids, d_bn, d_sorted, d_perm, d_codes,
+                            d_unique, d_conf, d_chash, d_vec);
 }
 
 extern "C" int eg_preencrypt_ballots(eg_ctx* c, const uint8_t K_be[512], size_t nb, size_t nc, const uint32_t* spc,
                                      uint32_t cb, const uint8_t* dcon, const uint8_t manifest_hash[32],
                                      const uint8_t* ids, const uint8_t* bn, uint8_t* sorted, uint32_t* perm,
                                      uint32_t* codes, uint8_t* unique, uint8_t* conf, uint8_t* chash, uint8_t* vec) {
-  int rc;
-  if ((rc = pre_check(c, nc, spc, nullptr, false, cb,
-                      K_be && (!nb || (dcon && manifest_hash && ids && bn && sorted && perm && codes && unique && conf)))))
-    return rc;
-  if (!nb) return EG_OK;
-  const PreShape P = pre_shape(nc, spc, nullptr);
-  const size_t nsel = P.M.nsel, V = P.V, chunk = pre_chunk(V), first = std::min(chunk, nb);
-  Locked L(c);
-  if ((rc = use_key_locked(c, K_be))) return rc;
-  uint8_t *d_desc = nullptr, *d_ids = nullptr, *d_bn = nullptr, *d_sorted = nullptr, *d_unique = nullptr,
-          *d_conf = nullptr, *d_chash = nullptr, *d_vec = nullptr;
-  uint32_t *d_perm = nullptr, *d_codes = nullptr;
-  if ((rc = ws_get(c, W_H0, (nc + 1) * 32, (void**)&d_desc))) return rc;  // [dcon nc][manifest_hash]
-  if ((rc = ws_get(c, W_H1, first * 32, (void**)&d_ids))) return rc;
-  if ((rc = ws_get(c, W_H2, first * 32, (void**)&d_bn))) return rc;
-  if ((rc = ws_get(c, W_H3, first * nsel * 32, (void**)&d_sorted))) return rc;
-  if ((rc = ws_get(c, W_H4, first * nsel * 4, (void**)&d_perm))) return rc;
-  if ((rc = ws_get(c, W_H5, first * nsel * 4, (void**)&d_codes))) return rc;
-  if ((rc = ws_get(c, W_H6, first, (void**)&d_unique))) return rc;
-  if ((rc = ws_get(c, W_EB0, first * 32, (void**)&d_conf))) return rc;
-  if ((rc = ws_get(c, W_EB1, first * nc * 32, (void**)&d_chash))) return rc;
-  if (vec && (rc = ws_get(c, W_EB2, first * V * 1024, (void**)&d_vec))) return rc;
-  HIPCHK(hipMemcpyAsync(d_desc, dcon, nc * 32, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(d_desc + nc * 32, manifest_hash, 32, hipMemcpyHostToDevice, c->stream));
-  // staged chunk by chunk: the device holds one chunk however many ballots come in
-  for (size_t b0 = 0; b0 < nb; b0 += chunk) {
-    const size_t n = std::min(chunk, nb - b0);
-    HIPCHK(hipMemcpyAsync(d_ids, ids + b0 * 32, n * 32, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_bn, bn + b0 * 32, n * 32, hipMemcpyHostToDevice, c->stream));
-    if ((rc = pre_chunk_locked(c, P, n, cb, d_desc, d_desc + nc * 32, d_ids, d_bn, d_sorted, d_perm, d_codes, d_unique,
-                               d_conf, d_chash, d_vec)))
-      return rc;
-    HIPCHK(hipMemcpyAsync(sorted + b0 * nsel * 32, d_sorted, n * nsel * 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(perm + b0 * nsel, d_perm, n * nsel * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(codes + b0 * nsel, d_codes, n * nsel * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(unique + b0, d_unique, n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(conf + b0 * 32, d_conf, n * 32, hipMemcpyDeviceToHost, c->stream));
-    if (chash) HIPCHK(hipMemcpyAsync(chash + b0 * nc * 32, d_chash, n * nc * 32, hipMemcpyDeviceToHost, c->stream));
-    if (vec) HIPCHK(hipMemcpyAsync(vec + b0 * V * 1024, d_vec, n * V * 1024, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-  }
-  return EG_OK;
+  return preencrypt_ballots(c, true, K_be, nb, nc, spc, cb, dcon, manifest_hash, ids, bn, sorted, perm, codes, unique,
+                            conf, chash, vec);
 }
 
 // ---------------------------------------------------------------------------------
@@ -296,76 +271,51 @@ static int record_chunk_locked(eg_ctx* c, const PreShape& P, size_t nbc, uint32_
   return EG_OK;
 }
 
+static int preencrypt_record(eg_ctx* c, bool host, const uint8_t* K_be, size_t nb, size_t nc, const uint32_t* spc,
+                             const uint32_t* limits, uint32_t cb, const uint8_t* dcon, const uint8_t* bn,
+                             const uint8_t* votes, const uint8_t* sorted, uint8_t* sv, uint32_t* rank, uint32_t* codes,
+                             uint8_t* sn, uint8_t* cn, uint8_t* ok) {
+  int rc;
+  if ((rc = pre_check(c, nc, spc, limits, true, cb,
+                      K_be && (!nb || (dcon && bn && votes && sorted && sv && rank && codes && sn && cn && ok)))))
+    return rc;
+  if (!host && !aligned16({dcon, bn, sorted, sv, sn, cn})) return pre_fail("device pointer not 16-byte aligned");
+  if (!nb) return EG_OK;
+  const PreShape P = pre_shape(nc, spc, limits);
+  const size_t nsel = P.M.nsel;
+  Locked L(c);
+  if ((rc = use_key_locked(c, K_be))) return rc;
+  Stage st(c, host, nb, pre_chunk(P.S));
+  st.once(dcon, nc * 32);
+  st.in(bn, 32);
+  st.in(votes, nsel);
+  st.in(sorted, nsel * 32);
+  st.out(sv, P.S * 1024);
+  st.out(rank, P.T * 4);
+  st.out(codes, P.T * 4);
+  st.out(sn, nsel * 128);
+  st.out(cn, nc * 32);
+  st.out(ok, nc);
+  return st.run([&](size_t n) {
+    return record_chunk_locked(c, P, n, cb, dcon, bn, votes, sorted, sv, rank, codes, sn, cn, ok);
+  });
+}
+
 extern "C" int eg_preencrypt_record_dev(eg_ctx* c, const uint8_t K_be[512], size_t nb, size_t nc, const uint32_t* spc,
                                         const uint32_t* limits, uint32_t cb, const uint8_t* d_dcon,
                                         const uint8_t* d_bn, const uint8_t* d_votes, const uint8_t* d_sorted,
                                         uint8_t* d_sv, uint32_t* d_rank, uint32_t* d_codes, uint8_t* d_sn,
                                         uint8_t* d_cn, uint8_t* d_ok) {
-  int rc;
-  if ((rc = pre_check(c, nc, spc, limits, true, cb,
-                      K_be && (!nb || (d_dcon && d_bn && d_votes && d_sorted && d_sv && d_rank && d_codes && d_sn &&
-                                       d_cn && d_ok)))))
-    return rc;
-  if (!aligned16({d_dcon, d_bn, d_sorted, d_sv, d_sn, d_cn})) return pre_fail("device pointer not 16-byte aligned");
-  if (!nb) return EG_OK;
-  const PreShape P = pre_shape(nc, spc, limits);
-  const size_t nsel = P.M.nsel, chunk = pre_chunk(P.S);
-  Locked L(c);
-  if ((rc = use_key_locked(c, K_be))) return rc;
-  for (size_t b0 = 0; b0 < nb; b0 += chunk) {
-    const size_t n = std::min(chunk, nb - b0);
-    if ((rc = record_chunk_locked(c, P, n, cb, d_dcon, d_bn + b0 * 32, d_votes + b0 * nsel, d_sorted + b0 * nsel * 32,
-                                  d_sv + b0 * P.S * 1024, d_rank + b0 * P.T, d_codes + b0 * P.T,
-                                  d_sn + b0 * nsel * 128, d_cn + b0 * nc * 32, d_ok + b0 * nc)))
-      return rc;
-  }
-  return EG_OK;
+  return preencrypt_record(c, false, K_be, nb, nc, spc, limits, cb, d_dcon, d_bn, d_votes, d_sorted, d_sv, d_rank,
+                           d_codes, d_sn, d_cn, d_ok);
 }
 
 extern "C" int eg_preencrypt_record(eg_ctx* c, const uint8_t K_be[512], size_t nb, size_t nc, const uint32_t* spc,
                                     const uint32_t* limits, uint32_t cb, const uint8_t* dcon, const uint8_t* bn,
                                     const uint8_t* votes, const uint8_t* sorted, uint8_t* sv, uint32_t* rank,
                                     uint32_t* codes, uint8_t* sn, uint8_t* cn, uint8_t* ok) {
-  int rc;
-  if ((rc = pre_check(c, nc, spc, limits, true, cb,
-                      K_be && (!nb || (dcon && bn && votes && sorted && sv && rank && codes && sn && cn && ok)))))
-    return rc;
-  if (!nb) return EG_OK;
-  const PreShape P = pre_shape(nc, spc, limits);
-  const size_t nsel = P.M.nsel, S = P.S, T = P.T, chunk = pre_chunk(S), first = std::min(chunk, nb);
-  Locked L(c);
-  if ((rc = use_key_locked(c, K_be))) return rc;
-  uint8_t *d_dcon = nullptr, *d_bn = nullptr, *d_votes = nullptr, *d_sorted = nullptr, *d_sv = nullptr, *d_sn = nullptr,
-          *d_cn = nullptr, *d_ok = nullptr;
-  uint32_t *d_rank = nullptr, *d_codes = nullptr;
-  if ((rc = ws_get(c, W_H0, nc * 32, (void**)&d_dcon))) return rc;
-  if ((rc = ws_get(c, W_H1, first * 32, (void**)&d_bn))) return rc;
-  if ((rc = ws_get(c, W_H2, first * nsel, (void**)&d_votes))) return rc;
-  if ((rc = ws_get(c, W_H3, first * nsel * 32, (void**)&d_sorted))) return rc;
-  if ((rc = ws_get(c, W_H4, first * T * 4, (void**)&d_rank))) return rc;
-  if ((rc = ws_get(c, W_H5, first * T * 4, (void**)&d_codes))) return rc;
-  if ((rc = ws_get(c, W_H6, first * nc, (void**)&d_ok))) return rc;
-  if ((rc = ws_get(c, W_EB0, first * S * 1024, (void**)&d_sv))) return rc;
-  if ((rc = ws_get(c, W_EB1, first * nsel * 128, (void**)&d_sn))) return rc;
-  if ((rc = ws_get(c, W_EB2, first * nc * 32, (void**)&d_cn))) return rc;
-  HIPCHK(hipMemcpyAsync(d_dcon, dcon, nc * 32, hipMemcpyHostToDevice, c->stream));
-  for (size_t b0 = 0; b0 < nb; b0 += chunk) {
-    const size_t n = std::min(chunk, nb - b0);
-    HIPCHK(hipMemcpyAsync(d_bn, bn + b0 * 32, n * 32, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_votes, votes + b0 * nsel, n * nsel, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_sorted, sorted + b0 * nsel * 32, n * nsel * 32, hipMemcpyHostToDevice, c->stream));
-    if ((rc = record_chunk_locked(c, P, n, cb, d_dcon, d_bn, d_votes, d_sorted, d_sv, d_rank, d_codes, d_sn, d_cn,
-                                  d_ok)))
-      return rc;
-    HIPCHK(hipMemcpyAsync(sv + b0 * S * 1024, d_sv, n * S * 1024, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(rank + b0 * T, d_rank, n * T * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(codes + b0 * T, d_codes, n * T * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(sn + b0 * nsel * 128, d_sn, n * nsel * 128, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(cn + b0 * nc * 32, d_cn, n * nc * 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(ok + b0 * nc, d_ok, n * nc, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-  }
-  return EG_OK;
+  return preencrypt_record(c, true, K_be, nb, nc, spc, limits, cb, dcon, bn, votes, sorted, sv, rank, codes, sn, cn,
+                           ok);
 }
 
 // ---------------------------------------------------------------------------------
@@ -442,30 +392,44 @@ static int preverify_chunk_locked(eg_ctx* c, const PreShape& P, size_t nbc, uint
   return EG_OK;
 }
 
+static int preencrypt_verify(eg_ctx* c, bool host, size_t nb, size_t nc, const uint32_t* spc, const uint32_t* limits,
+                             uint32_t cb, const uint8_t* dcon, const uint8_t* mh, const uint8_t* ids,
+                             const uint8_t* sv, const uint32_t* rank, const uint32_t* codes, const uint8_t* sorted,
+                             const uint8_t* cts, const uint8_t* conf, uint8_t* okc, uint8_t* okb) {
+  int rc;
+  if ((rc = pre_check(c, nc, spc, limits, true, cb,
+                      !nb || (dcon && mh && ids && sv && rank && codes && sorted && cts && conf && okc && okb))))
+    return rc;
+  if (!host && !aligned16({dcon, mh, ids, sv, sorted, cts, conf}))
+    return pre_fail("device pointer not 16-byte aligned");
+  if (!nb) return EG_OK;
+  const PreShape P = pre_shape(nc, spc, limits);
+  const size_t nsel = P.M.nsel;
+  Locked L(c);
+  Stage st(c, host, nb, pre_chunk(P.S));
+  st.once(dcon, nc * 32);
+  st.once(mh, 32);
+  st.in(ids, 32);
+  st.in(sv, P.S * 1024);
+  st.in(rank, P.T * 4);
+  st.in(codes, P.T * 4);
+  st.in(sorted, nsel * 32);
+  st.in(cts, nsel * 1024);
+  st.in(conf, 32);
+  st.out(okc, nc);
+  st.out(okb, 1);
+  return st.run([&](size_t n) {
+    return preverify_chunk_locked(c, P, n, cb, dcon, mh, ids, sv, rank, codes, sorted, cts, conf, okc, okb);
+  });
+}
+
 extern "C" int eg_preencrypt_verify_dev(eg_ctx* c, size_t nb, size_t nc, const uint32_t* spc, const uint32_t* limits,
                                         uint32_t cb, const uint8_t* d_dcon, const uint8_t* d_mh, const uint8_t* d_ids,
                                         const uint8_t* d_sv, const uint32_t* d_rank, const uint32_t* d_codes,
                                         const uint8_t* d_sorted, const uint8_t* d_cts, const uint8_t* d_conf,
                                         uint8_t* d_okc, uint8_t* d_okb) {
-  int rc;
-  if ((rc = pre_check(c, nc, spc, limits, true, cb,
-                      !nb || (d_dcon && d_mh && d_ids && d_sv && d_rank && d_codes && d_sorted && d_cts && d_conf &&
-                              d_okc && d_okb))))
-    return rc;
-  if (!aligned16({d_dcon, d_mh, d_ids, d_sv, d_sorted, d_cts, d_conf}))
-    return pre_fail("device pointer not 16-byte aligned");
-  if (!nb) return EG_OK;
-  const PreShape P = pre_shape(nc, spc, limits);
-  const size_t nsel = P.M.nsel, chunk = pre_chunk(P.S);
-  Locked L(c);
-  for (size_t b0 = 0; b0 < nb; b0 += chunk) {
-    const size_t n = std::min(chunk, nb - b0);
-    if ((rc = preverify_chunk_locked(c, P, n, cb, d_dcon, d_mh, d_ids + b0 * 32, d_sv + b0 * P.S * 1024,
-                                     d_rank + b0 * P.T, d_codes + b0 * P.T, d_sorted + b0 * nsel * 32,
-                                     d_cts + b0 * nsel * 1024, d_conf + b0 * 32, d_okc + b0 * nc, d_okb + b0)))
-      return rc;
-  }
-  return EG_OK;
+  return preencrypt_verify(c, false, nb, nc, spc, limits, cb, d_dcon, d_mh, d_ids, d_sv, d_rank, d_codes, d_sorted,
+                           d_cts, d_conf, d_okc, d_okb);
 }
 
 extern "C" int eg_preencrypt_verify(eg_ctx* c, size_t nb, size_t nc, const uint32_t* spc, const uint32_t* limits,
@@ -473,45 +437,6 @@ extern "C" int eg_preencrypt_verify(eg_ctx* c, size_t nb, size_t nc, const uint3
                                     const uint8_t* ids, const uint8_t* sv, const uint32_t* rank, const uint32_t* codes,
                                     const uint8_t* sorted, const uint8_t* cts, const uint8_t* conf, uint8_t* okc,
                                     uint8_t* okb) {
-  int rc;
-  if ((rc = pre_check(c, nc, spc, limits, true, cb,
-                      !nb || (dcon && manifest_hash && ids && sv && rank && codes && sorted && cts && conf && okc &&
-                              okb))))
-    return rc;
-  if (!nb) return EG_OK;
-  const PreShape P = pre_shape(nc, spc, limits);
-  const size_t nsel = P.M.nsel, S = P.S, T = P.T, chunk = pre_chunk(S), first = std::min(chunk, nb);
-  Locked L(c);
-  uint8_t *d_desc = nullptr, *d_ids = nullptr, *d_sv = nullptr, *d_sorted = nullptr, *d_cts = nullptr,
-          *d_conf = nullptr, *d_okc = nullptr, *d_okb = nullptr;
-  uint32_t *d_rank = nullptr, *d_codes = nullptr;
-  if ((rc = ws_get(c, W_H0, (nc + 1) * 32, (void**)&d_desc))) return rc;  // [dcon nc][manifest_hash]
-  if ((rc = ws_get(c, W_H1, first * 32, (void**)&d_ids))) return rc;
-  if ((rc = ws_get(c, W_H2, first * 32, (void**)&d_conf))) return rc;
-  if ((rc = ws_get(c, W_H3, first * nsel * 32, (void**)&d_sorted))) return rc;
-  if ((rc = ws_get(c, W_H4, first * T * 4, (void**)&d_rank))) return rc;
-  if ((rc = ws_get(c, W_H5, first * T * 4, (void**)&d_codes))) return rc;
-  if ((rc = ws_get(c, W_H6, first * nc, (void**)&d_okc))) return rc;
-  if ((rc = ws_get(c, W_EA2, first, (void**)&d_okb))) return rc;
-  if ((rc = ws_get(c, W_EB0, first * S * 1024, (void**)&d_sv))) return rc;
-  if ((rc = ws_get(c, W_EB1, first * nsel * 1024, (void**)&d_cts))) return rc;
-  HIPCHK(hipMemcpyAsync(d_desc, dcon, nc * 32, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(d_desc + nc * 32, manifest_hash, 32, hipMemcpyHostToDevice, c->stream));
-  for (size_t b0 = 0; b0 < nb; b0 += chunk) {
-    const size_t n = std::min(chunk, nb - b0);
-    HIPCHK(hipMemcpyAsync(d_ids, ids + b0 * 32, n * 32, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_conf, conf + b0 * 32, n * 32, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_sorted, sorted + b0 * nsel * 32, n * nsel * 32, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_rank, rank + b0 * T, n * T * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_codes, codes + b0 * T, n * T * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_sv, sv + b0 * S * 1024, n * S * 1024, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_cts, cts + b0 * nsel * 1024, n * nsel * 1024, hipMemcpyHostToDevice, c->stream));
-    if ((rc = preverify_chunk_locked(c, P, n, cb, d_desc, d_desc + nc * 32, d_ids, d_sv, d_rank, d_codes, d_sorted,
-                                     d_cts, d_conf, d_okc, d_okb)))
-      return rc;
-    HIPCHK(hipMemcpyAsync(okc + b0 * nc, d_okc, n * nc, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(okb + b0, d_okb, n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-  }
-  return EG_OK;
+  return preencrypt_verify(c, true, nb, nc, spc, limits, cb, dcon, manifest_hash, ids, sv, rank, codes, sorted, cts,
+                           conf, okc, okb);
 }

@@ -1,6 +1,8 @@
 // eg_capi_range.inc — 0..L range proofs of ciphertexts (include/eg_hip_range.h; included by
 // eg_capi.hip after eg_capi_contestdata.inc: the key, table, job-cache and launch helpers are
-// eg_capi_ballot.inc's, aligned16 is eg_capi_codes.inc's).  Kernels: eg_range.hpp and k_pow.
+// eg_capi_ballot.inc's).  Kernels: eg_range.hpp and k_pow.  eg_range_verify / eg_range_prove and
+// their _dev twins are one body each taking `bool host`, around one staged run (eg_stage.hpp) of
+// the chunk function.
 //
 // Verifier jobs per item (B = L + 1 branches).  Branches 0 and 1 are the selection verifier's
 // pair jobs, one per base: the alpha job is its SA shape (a_0, a_1; comb shared by e_0, e_1), the
@@ -24,8 +26,6 @@ static int range_args(eg_ctx* c, const uint8_t* K_be, const uint8_t* qbar_be, si
   if (L < 1 || L > EG_RANGE_MAX_LIMIT) return fail(EG_ERR_ARG, "range: limit outside [1, 15]");
   return EG_OK;
 }
-
-static inline unsigned rgrid(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 // ---------------------------------------------------------------------------------
 // verify
@@ -54,7 +54,7 @@ static int range_verify_chunk_locked(eg_ctx* c, size_t n, uint32_t L, const uint
   if ((rc = launch_import(c, d_cts, n * 2, E, LTP))) return rc;
   // 2. scalars: a working copy of the proofs (negated in place under EG_RESPONSE_PLUS), the g terms
   HIPCHK(hipMemcpyAsync(SC, d_proofs, n * B * 64, hipMemcpyDeviceToDevice, c->stream));
-  hipLaunchKernelGGL(k_range_scalars, dim3(rgrid(n)), dim3(kBlock), 0, c->stream, c->d_q, SC, (uint64_t)n, L,
+  hipLaunchKernelGGL(k_range_scalars, dim3(cgrid(n)), dim3(kBlock), 0, c->stream, c->d_q, SC, (uint64_t)n, L,
                      SC + off_g * 32, OKS, c->resp_plus);
   HIPCHK(hipGetLastError());
   // 3. commitments
@@ -107,53 +107,38 @@ static int range_verify_chunk_locked(eg_ctx* c, size_t n, uint32_t L, const uint
   HIPCHK(hipGetLastError());
   // 4. canonical bytes of the commitments, 5. the Fiat-Shamir check on the caller's proof rows
   if ((rc = launch_export(c, COMM, n * 2 * B, COMM_BE))) return rc;
-  hipLaunchKernelGGL(k_range_hash, dim3(rgrid(n)), dim3(kBlock), 0, c->stream, c->d_q, c->d_qbar, (uint64_t)n, L, d_cts,
+  hipLaunchKernelGGL(k_range_hash, dim3(cgrid(n)), dim3(kBlock), 0, c->stream, c->d_q, c->d_qbar, (uint64_t)n, L, d_cts,
                      COMM_BE, c->keys.front().d_K, c->pre_order, d_proofs, OKS, LTP, d_ok, (uint8_t*)nullptr,
                      c->hash_fmt);
   HIPCHK(hipGetLastError());
   return EG_OK;
 }
 
-extern "C" int eg_range_verify_dev(eg_ctx* c, const uint8_t K_be[512], const uint8_t qbar_be[32], size_t n, uint32_t L,
-                                   const uint8_t* d_cts, const uint8_t* d_proofs, uint8_t* d_ok) {
+// the key, qbar, then the items in chunks: in host mode the device holds one chunk however many come in
+static int range_verify(eg_ctx* c, bool host, const uint8_t* K_be, const uint8_t* qbar_be, size_t n, uint32_t L,
+                        const uint8_t* cts, const uint8_t* proofs, uint8_t* ok) {
   int rc;
-  if ((rc = range_args(c, K_be, qbar_be, n, L, d_cts && d_proofs && d_ok))) return rc;
-  if (!aligned16({d_cts, d_proofs})) return fail(EG_ERR_ARG, "range: device pointer not 16-byte aligned");
+  if ((rc = range_args(c, K_be, qbar_be, n, L, cts && proofs && ok))) return rc;
+  if (!host && !aligned16({cts, proofs})) return fail(EG_ERR_ARG, "range: device pointer not 16-byte aligned");
   if (!n) return EG_OK;
   Locked lk(c);
   if ((rc = use_key_locked(c, K_be))) return rc;
   HIPCHK(hipMemcpyAsync(c->d_qbar, qbar_be, 32, hipMemcpyHostToDevice, c->stream));
-  const size_t chunk = range_chunk(L), B = (size_t)L + 1;
-  for (size_t i0 = 0; i0 < n; i0 += chunk) {
-    const size_t m = std::min(chunk, n - i0);
-    if ((rc = range_verify_chunk_locked(c, m, L, d_cts + i0 * 1024, d_proofs + i0 * B * 64, d_ok + i0))) return rc;
-  }
-  return EG_OK;
+  Stage st(c, host, n, range_chunk(L));
+  st.in(cts, 1024);
+  st.in(proofs, ((size_t)L + 1) * 64);
+  st.out(ok, 1);
+  return st.run([&](size_t m) { return range_verify_chunk_locked(c, m, L, cts, proofs, ok); });
+}
+
+extern "C" int eg_range_verify_dev(eg_ctx* c, const uint8_t K_be[512], const uint8_t qbar_be[32], size_t n, uint32_t L,
+                                   const uint8_t* d_cts, const uint8_t* d_proofs, uint8_t* d_ok) {
+  return range_verify(c, false, K_be, qbar_be, n, L, d_cts, d_proofs, d_ok);
 }
 
 extern "C" int eg_range_verify(eg_ctx* c, const uint8_t K_be[512], const uint8_t qbar_be[32], size_t n, uint32_t L,
                                const uint8_t* cts, const uint8_t* proofs, uint8_t* ok) {
-  int rc;
-  if ((rc = range_args(c, K_be, qbar_be, n, L, cts && proofs && ok))) return rc;
-  if (!n) return EG_OK;
-  Locked lk(c);
-  if ((rc = use_key_locked(c, K_be))) return rc;
-  HIPCHK(hipMemcpyAsync(c->d_qbar, qbar_be, 32, hipMemcpyHostToDevice, c->stream));
-  const size_t chunk = range_chunk(L), B = (size_t)L + 1, first = std::min(chunk, n);
-  uint8_t *d_cts = nullptr, *d_pr = nullptr, *d_ok = nullptr;
-  if ((rc = ws_get(c, W_H0, first * 1024, (void**)&d_cts))) return rc;
-  if ((rc = ws_get(c, W_H1, first * B * 64, (void**)&d_pr))) return rc;
-  if ((rc = ws_get(c, W_H2, first, (void**)&d_ok))) return rc;
-  // staged chunk by chunk: the device holds one chunk however many items come in
-  for (size_t i0 = 0; i0 < n; i0 += chunk) {
-    const size_t m = std::min(chunk, n - i0);
-    HIPCHK(hipMemcpyAsync(d_cts, cts + i0 * 1024, m * 1024, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_pr, proofs + i0 * B * 64, m * B * 64, hipMemcpyHostToDevice, c->stream));
-    if ((rc = range_verify_chunk_locked(c, m, L, d_cts, d_pr, d_ok))) return rc;
-    HIPCHK(hipMemcpyAsync(ok + i0, d_ok, m, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-  }
-  return EG_OK;
+  return range_verify(c, true, K_be, qbar_be, n, L, cts, proofs, ok);
 }
 
 // ---------------------------------------------------------------------------------
@@ -181,7 +166,7 @@ static int range_prove_chunk_locked(eg_ctx* c, size_t n, uint32_t L, const uint8
   if ((rc = ws_get(c, W_BE0, oRE * 512, (void**)&COMM_BE))) return rc;
   if ((rc = ws_get(c, W_OK0, n * 32, (void**)&CH))) return rc;
   HIPCHK(hipMemcpyAsync(SC, d_nonces, n * nw * 32, hipMemcpyDeviceToDevice, c->stream));
-  hipLaunchKernelGGL(k_range_prep, dim3(rgrid(n)), dim3(kBlock), 0, c->stream, c->d_q, d_values, SC, d_R, (uint64_t)n,
+  hipLaunchKernelGGL(k_range_prep, dim3(cgrid(n)), dim3(kBlock), 0, c->stream, c->d_q, d_values, SC, d_R, (uint64_t)n,
                      L, SC + off_s * 32, SC + off_t * 32, c->resp_plus);
   HIPCHK(hipGetLastError());
   const std::string key = "rp/" + std::to_string(n) + "/" + std::to_string(L);
@@ -210,46 +195,28 @@ static int range_prove_chunk_locked(eg_ctx* c, size_t n, uint32_t L, const uint8
     if ((rc = launch_pow(c, S, jv[0], n * B, U, SC, U, G, K, nullptr, nullptr, &T, nullptr, ct))) return rc;
   }
   constexpr size_t kQuads = 2 * kW / 4;
-  hipLaunchKernelGGL(k_range_order, dim3(rgrid(n * kQuads)), dim3(kBlock), 0, c->stream, U, U + oRE * kW, d_values,
+  hipLaunchKernelGGL(k_range_order, dim3(cgrid(n * kQuads)), dim3(kBlock), 0, c->stream, U, U + oRE * kW, d_values,
                      (uint64_t)n, L);
   HIPCHK(hipGetLastError());
   if ((rc = launch_export(c, U, oRE, COMM_BE))) return rc;
-  hipLaunchKernelGGL(k_range_hash, dim3(rgrid(n)), dim3(kBlock), 0, c->stream, c->d_q, c->d_qbar, (uint64_t)n, L, d_cts,
+  hipLaunchKernelGGL(k_range_hash, dim3(cgrid(n)), dim3(kBlock), 0, c->stream, c->d_q, c->d_qbar, (uint64_t)n, L, d_cts,
                      COMM_BE, c->keys.front().d_K, c->pre_order, (const uint8_t*)nullptr, (const uint8_t*)nullptr,
                      (const uint8_t*)nullptr, (uint8_t*)nullptr, CH, c->hash_fmt);
-  hipLaunchKernelGGL(k_range_finish, dim3(rgrid(n)), dim3(kBlock), 0, c->stream, c->d_q, d_values, SC, d_R, CH,
+  hipLaunchKernelGGL(k_range_finish, dim3(cgrid(n)), dim3(kBlock), 0, c->stream, c->d_q, d_values, SC, d_R, CH,
                      (uint64_t)n, L, d_proofs, c->resp_plus);
   HIPCHK(hipGetLastError());
   return EG_OK;
 }
 
-extern "C" int eg_range_prove_dev(eg_ctx* c, const uint8_t K_be[512], const uint8_t qbar_be[32], size_t n, uint32_t L,
-                                  const uint8_t* d_cts, const uint8_t* d_values, const uint8_t* d_R,
-                                  const uint8_t* d_nonces, uint8_t* d_proofs) {
-  int rc;
-  if ((rc = range_args(c, K_be, qbar_be, n, L, d_cts && d_values && d_R && d_nonces && d_proofs))) return rc;
-  if (!aligned16({d_cts, d_R, d_nonces, d_proofs}))
-    return fail(EG_ERR_ARG, "range: device pointer not 16-byte aligned");
-  if (!n) return EG_OK;
-  Locked lk(c);
-  if ((rc = use_key_locked(c, K_be))) return rc;
-  HIPCHK(hipMemcpyAsync(c->d_qbar, qbar_be, 32, hipMemcpyHostToDevice, c->stream));
-  const size_t chunk = range_chunk(L), B = (size_t)L + 1;
-  for (size_t i0 = 0; i0 < n; i0 += chunk) {
-    const size_t m = std::min(chunk, n - i0);
-    if ((rc = range_prove_chunk_locked(c, m, L, d_cts + i0 * 1024, d_values + i0, d_R + i0 * 32,
-                                       d_nonces + i0 * (2 * B + 1) * 32, d_proofs + i0 * B * 64)))
-      return rc;
-  }
-  return EG_OK;
-}
-
-extern "C" int eg_range_prove(eg_ctx* c, const uint8_t K_be[512], const uint8_t qbar_be[32], size_t n, uint32_t L,
-                              const uint8_t* cts, const uint8_t* values, const uint8_t* R, const uint8_t* nonces,
-                              uint8_t* proofs) {
+// host values are checked here and name the item; device values past L give an all-zero proof
+static int range_prove(eg_ctx* c, bool host, const uint8_t* K_be, const uint8_t* qbar_be, size_t n, uint32_t L,
+                       const uint8_t* cts, const uint8_t* values, const uint8_t* R, const uint8_t* nonces,
+                       uint8_t* proofs) {
   int rc;
   if ((rc = range_args(c, K_be, qbar_be, n, L, cts && values && R && nonces && proofs))) return rc;
-  for (size_t i = 0; i < n; ++i)
+  if (!host && !aligned16({cts, R, nonces, proofs}))
+    return fail(EG_ERR_ARG, "range: device pointer not 16-byte aligned");
+  for (size_t i = 0; host && i < n; ++i)
     if (values[i] > L)
       return fail(EG_ERR_ARG, "range: values[" + std::to_string(i) + "] = " + std::to_string((unsigned)values[i]) +
                                   " exceeds the limit " + std::to_string(L));
@@ -257,22 +224,24 @@ extern "C" int eg_range_prove(eg_ctx* c, const uint8_t K_be[512], const uint8_t 
   Locked lk(c);
   if ((rc = use_key_locked(c, K_be))) return rc;
   HIPCHK(hipMemcpyAsync(c->d_qbar, qbar_be, 32, hipMemcpyHostToDevice, c->stream));
-  const size_t chunk = range_chunk(L), B = (size_t)L + 1, nw = 2 * B + 1, first = std::min(chunk, n);
-  uint8_t *d_cts = nullptr, *d_val = nullptr, *d_R = nullptr, *d_non = nullptr, *d_pr = nullptr;
-  if ((rc = ws_get(c, W_H0, first * 1024, (void**)&d_cts))) return rc;
-  if ((rc = ws_get(c, W_H1, first * B * 64, (void**)&d_pr))) return rc;
-  if ((rc = ws_get(c, W_H2, first, (void**)&d_val))) return rc;
-  if ((rc = ws_get(c, W_H3, first * 32, (void**)&d_R))) return rc;
-  if ((rc = ws_get(c, W_H4, first * nw * 32, (void**)&d_non))) return rc;
-  for (size_t i0 = 0; i0 < n; i0 += chunk) {
-    const size_t m = std::min(chunk, n - i0);
-    HIPCHK(hipMemcpyAsync(d_cts, cts + i0 * 1024, m * 1024, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_val, values + i0, m, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_R, R + i0 * 32, m * 32, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_non, nonces + i0 * nw * 32, m * nw * 32, hipMemcpyHostToDevice, c->stream));
-    if ((rc = range_prove_chunk_locked(c, m, L, d_cts, d_val, d_R, d_non, d_pr))) return rc;
-    HIPCHK(hipMemcpyAsync(proofs + i0 * B * 64, d_pr, m * B * 64, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-  }
-  return EG_OK;
+  const size_t B = (size_t)L + 1;
+  Stage st(c, host, n, range_chunk(L));
+  st.in(cts, 1024);
+  st.in(values, 1);
+  st.in(R, 32);
+  st.in(nonces, (2 * B + 1) * 32);
+  st.out(proofs, B * 64);
+  return st.run([&](size_t m) { return range_prove_chunk_locked(c, m, L, cts, values, R, nonces, proofs); });
+}
+
+extern "C" int eg_range_prove_dev(eg_ctx* c, const uint8_t K_be[512], const uint8_t qbar_be[32], size_t n, uint32_t L,
+                                  const uint8_t* d_cts, const uint8_t* d_values, const uint8_t* d_R,
+                                  const uint8_t* d_nonces, uint8_t* d_proofs) {
+  return range_prove(c, false, K_be, qbar_be, n, L, d_cts, d_values, d_R, d_nonces, d_proofs);
+}
+
+extern "C" int eg_range_prove(eg_ctx* c, const uint8_t K_be[512], const uint8_t qbar_be[32], size_t n, uint32_t L,
+                              const uint8_t* cts, const uint8_t* values, const uint8_t* R, const uint8_t* nonces,
+                              uint8_t* proofs) {
+  return range_prove(c, true, K_be, qbar_be, n, L, cts, values, R, nonces, proofs);
 }

@@ -336,3 +336,34 @@ def test_chain_tampering(group, chain5):
     seed = d["seed"].copy()
     seed[31] ^= 1
     assert _failed(verify(d["B"], d["codes"], seed)) == [0]
+
+
+# ---------------------------------------------------------------------------------------------
+# chunk crossing of the host-pointer variants
+# ---------------------------------------------------------------------------------------------
+def test_host_variants_one_ballot_more_than_a_chunk(fmt_group):
+    """16,385 ballots of one selection: the host variants stage 16,384-ballot chunks, so the last
+    ballot is a chunk of its own.  Against hashlib on both sides of the boundary, and against the
+    device variants (one launch / chunks of device pointers) over the whole batch."""
+    from electionguard import codes as C
+    g = fmt_group
+    nb = 16385
+    d = _data(_man([(1, 0)]), nb, 19)
+    man, h = d["man"], d["hashes"]
+    assert man.nsel == 1 and d["cts"].nbytes == nb * 1024
+    edge = [0, 16383, 16384, nb - 1]
+    sn, cn = C.derive_nonces(g, man, d["bn"])
+    B, hs, hc = C.ballot_hashes(g, man, h, d["ids"], d["cts"], parts=True)
+    B2 = C.ballot_hashes(g, man, h, d["ids"], d["cts"])
+    rsn, rcn = R.nonces(g.q, "fixed", man.spc_list, d["bn"][edge])
+    assert np.array_equal(sn[edge], rsn) and np.array_equal(cn[edge], rcn)
+    rB, rhs, rhc = R.hashes(g.q, "fixed", man.spc_list, h.dsel, h.dcon, h.manifest_hash, d["ids"][edge], d["cts"][edge])
+    assert np.array_equal(B[edge], rB) and np.array_equal(hs[edge], rhs) and np.array_equal(hc[edge], rhc)
+    assert np.array_equal(B2, B)
+    dsn, dcn = C.derive_nonces(g, man, g.to_device(d["bn"]))
+    assert np.array_equal(dsn.download(), sn) and np.array_equal(dcn.download(), cn)
+    d_ids, d_cts = g.to_device(d["ids"]), g.to_device(d["cts"])
+    dB, dhs, dhc = C.ballot_hashes(g, man, h, d_ids, d_cts, parts=True)
+    assert np.array_equal(dB.download(), B) and np.array_equal(dhs.download(), hs)
+    assert np.array_equal(dhc.download(), hc)
+    assert np.array_equal(C.ballot_hashes(g, man, h, d_ids, d_cts).download(), B)

@@ -1,8 +1,8 @@
 """GPU: pre-encrypted ballots (include/eg_hip_preencrypt.h, electionguard.preencrypt) against the
 reference of tests/preencrypt_ref.py frozen in tests/golden/Mode4096/preencrypt.json, the existing
 fixed-base / multiply batches and the host mirror: parity in both hash formats, partial last
-blocks, short codes, a chunk crossing, recording, tampering, constant-time mode, argument errors
-and the election-record hook."""
+blocks, short codes, a chunk crossing, recording, tampering, constant-time mode, argument errors,
+the election-record hook and the host variants' chunk crossings."""
 import copy
 import ctypes
 import json
@@ -385,3 +385,72 @@ def test_election_record_hook(group, env):
     bad_part.sel_rank[1, 0] ^= 1
     res = verify_election_record(group, er, preencrypted=bad_part)
     assert sorted(k for k, v in res.items() if not v) == ["preencrypted"]
+
+
+# ---------------------------------------------------------------------------------------------
+# chunk crossing of the host-pointer variants
+# ---------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def crossing(group, env):
+    """The (15, 1) manifest: 256 components and 16 chosen components per ballot, so pre-encryption
+    chunks by ballots_per_chunk(man) = 1,024 ballots, recording and the check by CHUNK_CTS // 16 =
+    16,384.  One ballot more than the larger chunk, pre-encrypted and recorded by the device
+    variants and downloaded once."""
+    from electionguard.ballot import ElectionManifest
+    from electionguard.codes import ManifestHashes
+    pe, _, key, *_ = env
+    man = ElectionManifest([(15, 1)])
+    sh = pe.pre_shape(man)
+    assert (sh.V, sh.S, sh.T) == (256, 16, 1)
+    chunk = pe.CHUNK_CTS // sh.S
+    nb = chunk + 1
+    rng = np.random.default_rng(257)
+    hashes = ManifestHashes(np.zeros((16, 32), np.uint8), rng.integers(0, 256, (1, 32), dtype=np.uint8),
+                            rng.integers(0, 256, 32, dtype=np.uint8))
+    ids = rng.integers(0, 256, (nb, 32), dtype=np.uint8)
+    bn = rng.integers(0, 128, (nb, 32), dtype=np.uint8)
+    votes = np.zeros((nb, 16), np.uint8)   # one vote per ballot, the placeholder included
+    votes[np.arange(nb), rng.integers(0, 16, nb)] = 1
+    d_bn = group.to_device(bn)
+    dpre = pe.preencrypt_ballots(group, key, man, hashes, group.to_device(ids), d_bn, 2)
+    pre = {f: getattr(dpre, f).download() for f in PRE_FIELDS}
+    drec = pe.record_parts(group, key, man, hashes, d_bn, group.to_device(votes), dpre.sorted, 2)
+    rec = {f: getattr(drec, f).download() for f in REC_FIELDS}
+    return man, hashes, ids, bn, votes, chunk, pre, rec
+
+
+def test_host_preencryption_one_ballot_more_than_a_chunk(group, env, crossing):
+    pe, _, key, *_ = env
+    man, hashes, ids, bn, _, _, pre, _ = crossing
+    nb = pe.ballots_per_chunk(man) + 1
+    host = pe.preencrypt_ballots(group, key, man, hashes, ids[:nb], bn[:nb], 2)
+    assert host.vec_cts is None
+    dev = pe.preencrypt_ballots(group, key, man, hashes, group.to_device(ids[:nb]), group.to_device(bn[:nb]), 2)
+    for f in PRE_FIELDS:
+        assert np.array_equal(getattr(host, f), getattr(dev, f).download()), f
+        assert np.array_equal(getattr(host, f), pre[f][:nb]), f
+
+
+def test_host_record_and_check_one_ballot_more_than_a_chunk(group, env, crossing):
+    pe, _, key, *_ = env
+    man, hashes, ids, bn, votes, chunk, pre, rec = crossing
+    nb = chunk + 1
+    host = pe.record_parts(group, key, man, hashes, bn, votes, pre["sorted"], 2)
+    assert host.ok.all()
+    for f in REC_FIELDS:
+        assert np.array_equal(getattr(host, f), rec[f]), f
+    # one chosen vector per contest (limit 1): the selections' ciphertexts are the chosen vectors
+    sv, rank, codes = rec["sel_vecs"], rec["sel_rank"], rec["sel_codes"]
+    okc, okb = pe.verify_recorded(group, man, hashes, ids, sv, rank, codes, pre["sorted"], sv, pre["conf"], 2)
+    assert okc.shape == (nb, 1) and okc.all() and okb.all()
+    # ballot `chunk` is the second chunk: a wrong rank, and a confirmation hash off by a bit
+    bad_rank, bad_conf = rank.copy(), pre["conf"].copy()
+    bad_rank[chunk, 0] ^= 1
+    bad_conf[chunk, 7] ^= 2
+    okc, okb = pe.verify_recorded(group, man, hashes, ids, sv, bad_rank, codes, pre["sorted"], sv, bad_conf, 2)
+    d_sv = group.to_device(sv)
+    dkc, dkb = pe.verify_recorded(group, man, hashes, group.to_device(ids), d_sv, group.to_device(bad_rank),
+                                  group.to_device(codes), group.to_device(pre["sorted"]), d_sv,
+                                  group.to_device(bad_conf), 2)
+    assert np.array_equal(okc, dkc.download().astype(bool)) and np.array_equal(okb, dkb.download().astype(bool))
+    assert np.flatnonzero(~okc[:, 0]).tolist() == [chunk] and np.flatnonzero(~okb).tolist() == [chunk]
