@@ -15,7 +15,6 @@ Selections are contest-major with the placeholder selection(s) last in each cont
 """
 from __future__ import annotations
 
-import ctypes
 from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple, Union
 
@@ -23,6 +22,7 @@ import numpy as np
 
 from .core import native
 from .core.group import GroupContext, p_bytes, q_bytes
+from .core.marshal import call, ptr, u32p
 
 
 @dataclass(frozen=True)
@@ -142,8 +142,14 @@ class ElectionManifest:
 AnyManifest = Union[Manifest, ElectionManifest]
 
 
-def _u32p(a: np.ndarray):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))
+def _entry(man: AnyManifest, base: str, verify: bool) -> Tuple[str, tuple]:
+    """The ballot entry point of man's type (a host name; its device variant adds "_dev") and the
+    shape arguments that follow nballots: scalars for a Manifest, per-contest tables for an
+    ElectionManifest."""
+    if isinstance(man, ElectionManifest):
+        tables = (man.placeholders, man.limits) if verify else ()
+        return base + "_manifest", (man.n_contests, u32p(man.spc_list), *map(u32p, tables))
+    return base, (man.n_contests, man.spc) + ((man.votes_allowed, man.votes_allowed) if verify else ())
 
 
 @dataclass
@@ -196,10 +202,6 @@ def random_votes(rng: np.random.Generator, man: AnyManifest, nb: int) -> np.ndar
     return v.reshape(nb, man.nsel)
 
 
-def _ptr(a: np.ndarray):
-    return a.ctypes.data_as(ctypes.c_void_p)
-
-
 class ElectionKey:
     """The joint election key K: registers its fixed-base table (window_bits wide) on a
     GroupContext.  Every ballot call passes K itself, and the library sets it under the ctx lock
@@ -235,18 +237,10 @@ def batch_encryption(group: GroupContext, key: ElectionKey, qbar: int, man: AnyM
     cts = np.empty((nb, man.nsel, 2, 512), dtype=np.uint8)
     rp = np.empty((nb, man.nsel, 4, 32), dtype=np.uint8)
     cp = np.empty((nb, man.n_contests, 2, 32), dtype=np.uint8)
-    if nb and isinstance(man, ElectionManifest):
-        native.check(group._lib, "eg_encrypt_ballots_manifest",
-                     group._lib.eg_encrypt_ballots_manifest(group.handle, native.buf(key.K_be),
-                                                            native.buf(q_bytes(qbar)), nb, man.n_contests,
-                                                            _u32p(man.spc_list), _ptr(votes), _ptr(sn), _ptr(cn),
-                                                            _ptr(cts), _ptr(rp), _ptr(cp)))
-    elif nb:
-        qb = q_bytes(qbar)
-        native.check(group._lib, "eg_encrypt_ballots",
-                     group._lib.eg_encrypt_ballots(group.handle, native.buf(key.K_be), native.buf(qb), nb,
-                                                   man.n_contests, man.spc, _ptr(votes), _ptr(sn), _ptr(cn), _ptr(cts),
-                                                   _ptr(rp), _ptr(cp)))
+    if nb:
+        name, shape = _entry(man, "eg_encrypt_ballots", verify=False)
+        call(group, name, native.buf(key.K_be), native.buf(q_bytes(qbar)), nb, *shape, ptr(votes), ptr(sn), ptr(cn),
+             ptr(cts), ptr(rp), ptr(cp))
     return EncryptedBallots(cts, rp, cp)
 
 
@@ -255,17 +249,10 @@ def batch_encryption_device(group: GroupContext, key: ElectionKey, qbar: int, ma
                             d_cproof: int) -> None:
     """batch_encryption on device pointers (e.g. torch tensors' data_ptr()): the same
     layouts, inputs and outputs resident in HBM (eg_encrypt_ballots_dev)."""
-    if nb and isinstance(man, ElectionManifest):
-        native.check(group._lib, "eg_encrypt_ballots_manifest_dev",
-                     group._lib.eg_encrypt_ballots_manifest_dev(group.handle, native.buf(key.K_be),
-                                                                native.buf(q_bytes(qbar)), nb, man.n_contests,
-                                                                _u32p(man.spc_list), d_votes, d_sel_nonces,
-                                                                d_contest_nonces, d_cts, d_rproof, d_cproof))
-    elif nb:
-        native.check(group._lib, "eg_encrypt_ballots_dev",
-                     group._lib.eg_encrypt_ballots_dev(group.handle, native.buf(key.K_be), native.buf(q_bytes(qbar)),
-                                                       nb, man.n_contests, man.spc, d_votes, d_sel_nonces,
-                                                       d_contest_nonces, d_cts, d_rproof, d_cproof))
+    if nb:
+        name, shape = _entry(man, "eg_encrypt_ballots", verify=False)
+        call(group, name + "_dev", native.buf(key.K_be), native.buf(q_bytes(qbar)), nb, *shape, d_votes, d_sel_nonces,
+             d_contest_nonces, d_cts, d_rproof, d_cproof)
 
 
 class Verifier:
@@ -274,10 +261,6 @@ class Verifier:
     def __init__(self, group: GroupContext, key: ElectionKey, qbar: int, man: AnyManifest):
         self.group, self.key, self.qbar, self.man = group, key, int(qbar), man
         self._qb = q_bytes(qbar)
-
-    def _shape_args(self):
-        man = self.man
-        return man.n_contests, _u32p(man.spc_list), _u32p(man.placeholders), _u32p(man.limits)
 
     def verify(self, eb: EncryptedBallots, with_tally: bool = True,
                cast: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
@@ -295,36 +278,18 @@ class Verifier:
         ok_s = np.zeros((nb, man.nsel), dtype=np.uint8)
         ok_c = np.zeros((nb, man.n_contests), dtype=np.uint8)
         tally = np.empty((man.n_real, 2, 512), dtype=np.uint8) if with_tally else None
-        if isinstance(man, ElectionManifest):
-            native.check(g._lib, "eg_verify_ballots_manifest",
-                         g._lib.eg_verify_ballots_manifest(g.handle, native.buf(self.key.K_be), native.buf(self._qb),
-                                                           nb, *self._shape_args(), _ptr(cts), _ptr(rp), _ptr(cp),
-                                                           _ptr(cm) if cm is not None else None, _ptr(ok_s),
-                                                           _ptr(ok_c), _ptr(tally) if tally is not None else None))
-            return ok_s.astype(bool), ok_c.astype(bool), tally
-        native.check(g._lib, "eg_verify_ballots",
-                     g._lib.eg_verify_ballots(g.handle, native.buf(self.key.K_be), native.buf(self._qb), nb,
-                                              man.n_contests, man.spc, man.votes_allowed, man.votes_allowed, _ptr(cts),
-                                              _ptr(rp), _ptr(cp), _ptr(cm) if cm is not None else None, _ptr(ok_s),
-                                              _ptr(ok_c), _ptr(tally) if tally is not None else None))
+        name, shape = _entry(man, "eg_verify_ballots", verify=True)
+        call(g, name, native.buf(self.key.K_be), native.buf(self._qb), nb, *shape, ptr(cts), ptr(rp), ptr(cp),
+             ptr(cm) if cm is not None else None, ptr(ok_s), ptr(ok_c), ptr(tally) if tally is not None else None)
         return ok_s.astype(bool), ok_c.astype(bool), tally
 
     def verify_device(self, d_cts: int, d_rproof: int, d_cproof: int, nb: int, d_ok_sel: int, d_ok_con: int,
                       d_tally: Optional[int], d_cast: Optional[int] = None) -> None:
         """Asynchronous verify on device pointers (e.g. torch CUDA tensors' data_ptr()); d_cast
         (nb bytes, 0 = spoiled) as verify's cast."""
-        man, g = self.man, self.group
-        if isinstance(man, ElectionManifest):
-            native.check(g._lib, "eg_verify_ballots_manifest_dev",
-                         g._lib.eg_verify_ballots_manifest_dev(g.handle, native.buf(self.key.K_be),
-                                                               native.buf(self._qb), nb, *self._shape_args(), d_cts,
-                                                               d_rproof, d_cproof, d_cast, d_ok_sel, d_ok_con,
-                                                               d_tally))
-            return
-        native.check(g._lib, "eg_verify_ballots_dev",
-                     g._lib.eg_verify_ballots_dev(g.handle, native.buf(self.key.K_be), native.buf(self._qb), nb,
-                                                  man.n_contests, man.spc, man.votes_allowed, man.votes_allowed, d_cts,
-                                                  d_rproof, d_cproof, d_cast, d_ok_sel, d_ok_con, d_tally))
+        name, shape = _entry(self.man, "eg_verify_ballots", verify=True)
+        call(self.group, name + "_dev", native.buf(self.key.K_be), native.buf(self._qb), nb, *shape, d_cts, d_rproof,
+             d_cproof, d_cast, d_ok_sel, d_ok_con, d_tally)
 
 
 def accumulate_tally(group: GroupContext, man: AnyManifest, eb: EncryptedBallots,

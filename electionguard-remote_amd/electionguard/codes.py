@@ -27,10 +27,10 @@ from typing import Sequence, Tuple, Union
 
 import numpy as np
 
-from .ballot import (AnyManifest, ElectionKey, EncryptedBallots, _ptr, _u32p, batch_encryption_device)
-from .core import native
-from .core.group import DeviceBuffer, FixedBase, GroupContext
+from .ballot import AnyManifest, ElectionKey, EncryptedBallots, batch_encryption_device
+from .core.group import FixedBase, GroupContext
 from .core.hashing import hash_elems
+from .core.marshal import Columns, be32_row as _b32, be_int as _i, q_row, rows32, u32p
 
 Q32 = Union[int, bytes, bytearray, np.ndarray]
 
@@ -46,46 +46,25 @@ class ManifestHashes:
 # ---------------------------------------------------------------------------------------------
 # small conversions
 # ---------------------------------------------------------------------------------------------
-def _q32(x: Q32) -> np.ndarray:
-    """One 32-byte element: an integer (big-endian) or 32 bytes as given."""
-    if isinstance(x, (int, np.integer)):
-        return np.frombuffer(int(x).to_bytes(32, "big"), np.uint8)
-    a = np.frombuffer(bytes(x), np.uint8) if isinstance(x, (bytes, bytearray)) else np.asarray(x, np.uint8)
-    if a.shape != (32,):
-        raise ValueError("a Q element is 32 bytes")
-    return a
-
-
-def _rows32(a, n: int, what: str) -> np.ndarray:
-    a = np.ascontiguousarray(a, dtype=np.uint8)
-    if a.size != n * 32:
-        raise ValueError(f"{what}: expected {n} x 32 bytes, got {a.size}")
-    return a.reshape(n, 32)
-
-
 def timestamp_elements(seconds: Sequence[int]) -> np.ndarray:
     """Integer seconds -> the (nb, 32) big-endian ts elements of the code chain."""
     return np.frombuffer(b"".join(int(t).to_bytes(32, "big") for t in seconds), np.uint8).reshape(-1, 32)
 
 
-def _ts_rows(timestamps, nb: int) -> np.ndarray:
+def _ts_elements(timestamps) -> np.ndarray:
     a = np.asarray(timestamps)
     if a.dtype != np.uint8 or a.ndim != 2:
         a = timestamp_elements([int(t) for t in a.reshape(-1)])
-    return _rows32(a, nb, "timestamps")
+    return a
 
 
-def _i(row) -> int:
-    return int.from_bytes(bytes(row), "big")
-
-
-def _b32(x: int) -> np.ndarray:
-    return np.frombuffer(int(x).to_bytes(32, "big"), np.uint8)
+def _ts_rows(timestamps, nb: int) -> np.ndarray:
+    return rows32(_ts_elements(timestamps), nb, "timestamps")
 
 
 def _hashes_rows(man: AnyManifest, hashes: ManifestHashes) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-    return (_rows32(hashes.dsel, man.nsel, "dsel"), _rows32(hashes.dcon, man.n_contests, "dcon"),
-            _q32(hashes.manifest_hash))
+    return (rows32(hashes.dsel, man.nsel, "dsel"), rows32(hashes.dcon, man.n_contests, "dcon"),
+            q_row(hashes.manifest_hash))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -112,7 +91,7 @@ def ballot_hashes_host(q: int, man: AnyManifest, hashes: ManifestHashes, ballot_
     nsel, nc = man.nsel, man.n_contests
     cts = np.ascontiguousarray(cts, dtype=np.uint8).reshape(-1, nsel, 2, 512)
     nb = len(cts)
-    ids = _rows32(ballot_ids, nb, "ballot_ids")
+    ids = rows32(ballot_ids, nb, "ballot_ids")
     dsel, dcon, mh = _hashes_rows(man, hashes)
     B = np.empty((nb, 32), np.uint8)
     hs = np.empty((nb, nsel, 32), np.uint8)
@@ -134,7 +113,7 @@ def chain_codes(q: int, seed: Q32, timestamps, ballot_hashes, fmt: str = "fixed"
     B = np.ascontiguousarray(ballot_hashes, dtype=np.uint8).reshape(-1, 32)
     ts = _ts_rows(timestamps, len(B))
     codes = np.empty((len(B), 32), np.uint8)
-    prev = _i(_q32(seed))
+    prev = _i(q_row(seed))
     for b in range(len(B)):
         prev = hash_elems(q, ("Q", prev), ("Q", _i(ts[b])), ("Q", _i(B[b])), fmt=fmt)
         codes[b] = _b32(prev)
@@ -145,10 +124,10 @@ def verify_code_chain_host(q: int, seed: Q32, timestamps, ballot_hashes, codes, 
     """-> ok (nb,) bool: codes[b] == H(codes[b-1] or seed, ts[b], B[b]) with the RECORDED codes[b-1]."""
     B = np.ascontiguousarray(ballot_hashes, dtype=np.uint8).reshape(-1, 32)
     nb = len(B)
-    ts, cd = _ts_rows(timestamps, nb), _rows32(codes, nb, "codes")
+    ts, cd = _ts_rows(timestamps, nb), rows32(codes, nb, "codes")
     ok = np.zeros(nb, bool)
     for b in range(nb):
-        prev = _i(cd[b - 1]) if b else _i(_q32(seed))
+        prev = _i(cd[b - 1]) if b else _i(q_row(seed))
         ok[b] = bytes(cd[b]) == bytes(_b32(hash_elems(q, ("Q", prev), ("Q", _i(ts[b])), ("Q", _i(B[b])), fmt=fmt)))
     return ok
 
@@ -156,24 +135,13 @@ def verify_code_chain_host(q: int, seed: Q32, timestamps, ballot_hashes, codes, 
 # ---------------------------------------------------------------------------------------------
 # GPU calls (numpy arrays through the host entry points, DeviceBuffers through the _dev ones)
 # ---------------------------------------------------------------------------------------------
-def _call(group: GroupContext, name: str, *args) -> None:
-    native.check(group._lib, name, getattr(group._lib, name)(group.handle, *args))
-
-
 def derive_nonces(group: GroupContext, man: AnyManifest, ballot_nonces):
     """-> (sel_nonces (nb, nsel, 4, 32), contest_nonces (nb, nc, 32)) of the ballot nonces (nb, 32);
     DeviceBuffers in, DeviceBuffers out (asynchronous on the context's stream)."""
-    nsel, nc = man.nsel, man.n_contests
-    if isinstance(ballot_nonces, DeviceBuffer):
-        nb = ballot_nonces.nbytes // 32
-        sn, cn = group.device_empty((nb, nsel, 4, 32)), group.device_empty((nb, nc, 32))
-        _call(group, "eg_derive_ballot_nonces_dev", nb, nc, _u32p(man.spc_list), ballot_nonces.ptr, sn.ptr, cn.ptr)
-        return sn, cn
-    bn = np.ascontiguousarray(ballot_nonces, dtype=np.uint8).reshape(-1, 32)
-    nb = len(bn)
-    sn, cn = np.empty((nb, nsel, 4, 32), np.uint8), np.empty((nb, nc, 32), np.uint8)
-    _call(group, "eg_derive_ballot_nonces", nb, nc, _u32p(man.spc_list), _ptr(bn), _ptr(sn), _ptr(cn))
-    return sn, cn
+    cols = Columns(group)
+    bn = cols.item(ballot_nonces, (32,), "ballot_nonces")
+    sn, cn = cols.out((man.nsel, 4, 32)), cols.out((man.n_contests, 32))
+    return tuple(cols.call("eg_derive_ballot_nonces", cols.n, man.n_contests, u32p(man.spc_list), bn, sn, cn))
 
 
 def ballot_hashes(group: GroupContext, man: AnyManifest, hashes: ManifestHashes, ballot_ids, cts, parts: bool = False):
@@ -181,46 +149,24 @@ def ballot_hashes(group: GroupContext, man: AnyManifest, hashes: ManifestHashes,
     ballot_ids DeviceBuffers the ciphertexts are hashed where they lie and the results are
     DeviceBuffers (asynchronous on the context's stream)."""
     nsel, nc = man.nsel, man.n_contests
-    dsel, dcon, mh = _hashes_rows(man, hashes)
-    if isinstance(cts, DeviceBuffer):
-        if not isinstance(ballot_ids, DeviceBuffer):
-            raise TypeError("device ciphertexts need device ballot ids")
-        nb = cts.nbytes // (nsel * 1024)
-        if ballot_ids.nbytes != nb * 32:
-            raise ValueError(f"ballot_ids: expected {nb} x 32 bytes, got {ballot_ids.nbytes}")
-        desc = group.to_device(np.concatenate([dsel.reshape(-1), dcon.reshape(-1), mh]))  # 32-byte rows
-        B = group.device_empty((nb, 32))
-        hs = group.device_empty((nb, nsel, 32)) if parts else None
-        hc = group.device_empty((nb, nc, 32)) if parts else None
-        _call(group, "eg_ballot_hashes_dev", nb, nc, _u32p(man.spc_list), desc.ptr, desc.ptr + nsel * 32,
-              desc.ptr + (nsel + nc) * 32, ballot_ids.ptr, cts.ptr, B.ptr, hs.ptr if parts else None,
-              hc.ptr if parts else None)
-        return (B, hs, hc) if parts else B  # desc's free waits for the stream (eg_dev_free)
-    cts = np.ascontiguousarray(cts, dtype=np.uint8).reshape(-1, nsel, 2, 512)
-    nb = len(cts)
-    ids = _rows32(ballot_ids, nb, "ballot_ids")
-    B = np.empty((nb, 32), np.uint8)
-    hs = np.empty((nb, nsel, 32), np.uint8) if parts else None
-    hc = np.empty((nb, nc, 32), np.uint8) if parts else None
-    _call(group, "eg_ballot_hashes", nb, nc, _u32p(man.spc_list), _ptr(dsel), _ptr(dcon), _ptr(mh), _ptr(ids),
-          _ptr(cts), _ptr(B), _ptr(hs) if parts else None, _ptr(hc) if parts else None)
-    return (B, hs, hc) if parts else B
+    cols = Columns(group)
+    dsel, dcon, mh = map(cols.once, _hashes_rows(man, hashes))
+    cts = cols.item(cts, (nsel, 2, 512), "cts")
+    ids = cols.item(ballot_ids, (32,), "ballot_ids")
+    B, hs, hc = cols.out((32,)), cols.out((nsel, 32), want=parts), cols.out((nc, 32), want=parts)
+    out = cols.call("eg_ballot_hashes", cols.n, nc, u32p(man.spc_list), dsel, dcon, mh, ids, cts, B, hs, hc)
+    return tuple(out) if parts else out[0]
 
 
 def verify_code_chain(group: GroupContext, seed: Q32, timestamps, ballot_hashes, codes):
     """-> ok (nb,) bool: every link of the chain recomputed from the recorded previous code.  With
     DeviceBuffers for all four (seed too) -> a DeviceBuffer of nb flag bytes, asynchronous."""
-    if isinstance(codes, DeviceBuffer):
-        nb = codes.nbytes // 32
-        ok = group.device_empty((nb,))
-        _call(group, "eg_verify_code_chain_dev", nb, seed.ptr, timestamps.ptr, ballot_hashes.ptr, codes.ptr, ok.ptr)
-        return ok
-    B = np.ascontiguousarray(ballot_hashes, dtype=np.uint8).reshape(-1, 32)
-    nb = len(B)
-    ts, cd, sd = _ts_rows(timestamps, nb), _rows32(codes, nb, "codes"), np.ascontiguousarray(_q32(seed))
-    ok = np.zeros(nb, np.uint8)
-    _call(group, "eg_verify_code_chain", nb, _ptr(sd), _ptr(ts), _ptr(B), _ptr(cd), _ptr(ok))
-    return ok.astype(bool)
+    cols = Columns(group)
+    B = cols.item(ballot_hashes, (32,), "ballot_hashes")
+    ts = cols.item(timestamps, (32,), "timestamps", host=_ts_elements)
+    cd = cols.item(codes, (32,), "codes")
+    sd = cols.given(seed, "seed")
+    return cols.call("eg_verify_code_chain", cols.n, sd, ts, B, cd, cols.out((), flag=True))[0]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -236,8 +182,8 @@ def encrypt_ballots_seeded(group: GroupContext, key: ElectionKey, qbar: int, man
     nsel, nc = man.nsel, man.n_contests
     votes = np.ascontiguousarray(votes, dtype=np.uint8).reshape(-1, nsel)
     nb = len(votes)
-    bn = _rows32(ballot_nonces, nb, "ballot_nonces")
-    ids = _rows32(ballot_ids, nb, "ballot_ids")
+    bn = rows32(ballot_nonces, nb, "ballot_nonces")
+    ids = rows32(ballot_ids, nb, "ballot_ids")
     if not nb:
         eb = EncryptedBallots(np.empty((0, nsel, 2, 512), np.uint8), np.empty((0, nsel, 4, 32), np.uint8),
                               np.empty((0, nc, 2, 32), np.uint8))
@@ -261,7 +207,7 @@ def open_ballots(group: GroupContext, key: ElectionKey, man: AnyManifest, eb: En
     nsel = man.nsel
     cts = np.ascontiguousarray(eb.cts, dtype=np.uint8).reshape(-1, nsel, 2, 512)
     nb = len(cts)
-    bn = _rows32(ballot_nonces, nb, "ballot_nonces")
+    bn = rows32(ballot_nonces, nb, "ballot_nonces")
     if not nb:
         return np.zeros((0, nsel), np.uint8), np.zeros((0, nsel), bool)
     sn, _ = derive_nonces(group, man, bn)

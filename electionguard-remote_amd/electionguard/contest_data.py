@@ -33,11 +33,11 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .ballot import AnyManifest, ElectionKey, _ptr
-from .codes import _call, _rows32
+from .ballot import AnyManifest, ElectionKey
 from .core import native
-from .core.group import DeviceBuffer, FixedBase, GroupContext
+from .core.group import FixedBase, GroupContext
 from .core.hashing import hash_elems
+from .core.marshal import Columns, be_int as _i, rows32
 
 MAX_BYTES = 1024   # EG_CD_MAX_BYTES
 TAG = b"contest"
@@ -131,10 +131,6 @@ def _be32(x: int) -> bytes:
     return int(x).to_bytes(4, "big")
 
 
-def _i(row) -> int:
-    return int.from_bytes(bytes(row), "big")
-
-
 def derive_nonces_host(q: int, ncontest: int, ballot_nonces, fmt: str = "fixed") -> np.ndarray:
     """-> r (nb, nc, 32)"""
     bn = np.ascontiguousarray(ballot_nonces, dtype=np.uint8).reshape(-1, 32)
@@ -172,7 +168,7 @@ def _shapes(ncontest: int, ballot_ids, c0, kappa, rows):
     kappa = np.ascontiguousarray(kappa, dtype=np.uint8).reshape(-1, 512)
     if len(kappa) != n:
         raise ValueError("one kappa per item")
-    return _rows32(ballot_ids, n // ncontest, "ballot_ids"), c0, kappa, rows
+    return rows32(ballot_ids, n // ncontest, "ballot_ids"), c0, kappa, rows
 
 
 def seal_host(ncontest: int, ballot_ids, c0, kappa, data) -> Tuple[np.ndarray, np.ndarray]:
@@ -190,7 +186,7 @@ def seal_host(ncontest: int, ballot_ids, c0, kappa, data) -> Tuple[np.ndarray, n
 def open_host(ncontest: int, ballot_ids, c0, kappa, c1, c2) -> Tuple[np.ndarray, np.ndarray]:
     """-> data (n, nbytes), ok (n,) bool; a failed item's row is zero"""
     ids, c0, kappa, c1 = _shapes(ncontest, ballot_ids, c0, kappa, c1)
-    c2 = _rows32(c2, len(c1), "c2")
+    c2 = rows32(c2, len(c1), "c2")
     data, ok = np.zeros_like(c1), np.zeros(len(c1), bool)
     for i in range(len(c1)):
         kk, mk, label = item_keys_host(c0[i], kappa[i], ids[i // ncontest], i % ncontest)
@@ -223,15 +219,9 @@ def _nbytes(nbytes: int) -> int:
 def derive_nonces(group: GroupContext, ncontest: int, ballot_nonces):
     """-> r (nb, nc, 32) of the ballot nonces (nb, 32); a DeviceBuffer in, a DeviceBuffer out
     (asynchronous on the context's stream)."""
-    if isinstance(ballot_nonces, DeviceBuffer):
-        nb = ballot_nonces.nbytes // 32
-        r = group.device_empty((nb, ncontest, 32))
-        _call(group, "eg_derive_contest_data_nonces_dev", nb, ncontest, ballot_nonces.ptr, r.ptr)
-        return r
-    bn = np.ascontiguousarray(ballot_nonces, dtype=np.uint8).reshape(-1, 32)
-    r = np.empty((len(bn), ncontest, 32), np.uint8)
-    _call(group, "eg_derive_contest_data_nonces", len(bn), ncontest, _ptr(bn), _ptr(r))
-    return r
+    cols = Columns(group)
+    bn = cols.item(ballot_nonces, (32,), "ballot_nonces")
+    return cols.call("eg_derive_contest_data_nonces", cols.n, ncontest, bn, cols.out((ncontest, 32)))[0]
 
 
 def seal(group: GroupContext, key: ElectionKey, ncontest: int, nbytes: int, ballot_ids, nonces_r, data):
@@ -239,29 +229,13 @@ def seal(group: GroupContext, key: ElectionKey, ncontest: int, nbytes: int, ball
     With DeviceBuffers for the three inputs the results are DeviceBuffers (asynchronous).  The two
     exponentiations follow group.ct_pow."""
     nbytes = _nbytes(nbytes)
-    K = native.buf(key.K_be)
-    if isinstance(data, DeviceBuffer):
-        if not (isinstance(ballot_ids, DeviceBuffer) and isinstance(nonces_r, DeviceBuffer)):
-            raise TypeError("device data needs device ballot ids and nonces")
-        nb = ballot_ids.nbytes // 32
-        n = nb * ncontest
-        if data.nbytes != n * nbytes or nonces_r.nbytes != n * 32:
-            raise ValueError(f"expected {n} items of {nbytes} bytes and {n} nonces")
-        c0, c1, c2 = group.device_empty((n, 512)), group.device_empty((n, nbytes)), group.device_empty((n, 32))
-        _call(group, "eg_seal_contest_data_dev", K, nb, ncontest, nbytes, ballot_ids.ptr, nonces_r.ptr, data.ptr,
-              c0.ptr, c1.ptr, c2.ptr)
-        return c0, c1, c2
-    ids = np.ascontiguousarray(ballot_ids, dtype=np.uint8).reshape(-1, 32)
-    nb = len(ids)
-    n = nb * ncontest
-    r = _rows32(nonces_r, n, "nonces_r")
-    data = np.ascontiguousarray(data, dtype=np.uint8)
-    if data.size != n * nbytes:
-        raise ValueError(f"data: expected {n} x {nbytes} bytes, got {data.size}")
-    c0, c1, c2 = np.empty((n, 512), np.uint8), np.empty((n, nbytes), np.uint8), np.empty((n, 32), np.uint8)
-    _call(group, "eg_seal_contest_data", K, nb, ncontest, nbytes, _ptr(ids), _ptr(r), _ptr(data), _ptr(c0), _ptr(c1),
-          _ptr(c2))
-    return c0, c1, c2
+    cols = Columns(group)
+    ids = cols.item(ballot_ids, (32,), "ballot_ids")
+    r = cols.item(nonces_r, (ncontest, 32), "nonces_r")
+    data = cols.item(data, (ncontest, nbytes), "data")
+    c0, c1, c2 = (cols.out((w,), per=ncontest) for w in (512, nbytes, 32))
+    return tuple(cols.call("eg_seal_contest_data", native.buf(key.K_be), cols.n, ncontest, nbytes, ids, r, data,
+                           c0, c1, c2))
 
 
 def open_sealed(group: GroupContext, ncontest: int, nbytes: int, ballot_ids, c0, kappa, c1, c2):
@@ -269,30 +243,12 @@ def open_sealed(group: GroupContext, ncontest: int, nbytes: int, ballot_ids, c0,
     fails has ok False and a zero row; the others are not affected.  With DeviceBuffers for all
     five inputs -> DeviceBuffers (ok as flag bytes), asynchronous."""
     nbytes = _nbytes(nbytes)
-    if isinstance(c1, DeviceBuffer):
-        if not all(isinstance(x, DeviceBuffer) for x in (ballot_ids, c0, kappa, c2)):
-            raise TypeError("device ciphertexts need device ballot ids, c0, kappa and c2")
-        nb = ballot_ids.nbytes // 32
-        n = nb * ncontest
-        if c0.nbytes != n * 512 or kappa.nbytes != n * 512 or c1.nbytes != n * nbytes or c2.nbytes != n * 32:
-            raise ValueError(f"expected {n} items of {nbytes} bytes")
-        data, ok = group.device_empty((n, nbytes)), group.device_empty((n,))
-        _call(group, "eg_open_contest_data_dev", nb, ncontest, nbytes, ballot_ids.ptr, c0.ptr, kappa.ptr, c1.ptr,
-              c2.ptr, data.ptr, ok.ptr)
-        return data, ok
-    ids = np.ascontiguousarray(ballot_ids, dtype=np.uint8).reshape(-1, 32)
-    nb = len(ids)
-    n = nb * ncontest
-    c0 = np.ascontiguousarray(c0, dtype=np.uint8)
-    kappa = np.ascontiguousarray(kappa, dtype=np.uint8)
-    c1 = np.ascontiguousarray(c1, dtype=np.uint8)
-    c2 = _rows32(c2, n, "c2")
-    if c0.size != n * 512 or kappa.size != n * 512 or c1.size != n * nbytes:
-        raise ValueError(f"expected {n} items of {nbytes} bytes")
-    data, ok = np.zeros((n, nbytes), np.uint8), np.zeros(n, np.uint8)
-    _call(group, "eg_open_contest_data", nb, ncontest, nbytes, _ptr(ids), _ptr(c0), _ptr(kappa), _ptr(c1), _ptr(c2),
-          _ptr(data), _ptr(ok))
-    return data, ok.astype(bool)
+    cols = Columns(group)
+    ids = cols.item(ballot_ids, (32,), "ballot_ids")
+    c0, kappa = cols.item(c0, (ncontest, 512), "c0"), cols.item(kappa, (ncontest, 512), "kappa")
+    c1, c2 = cols.item(c1, (ncontest, nbytes), "c1"), cols.item(c2, (ncontest, 32), "c2")
+    data, ok = cols.out((nbytes,), per=ncontest), cols.out((), per=ncontest, flag=True)
+    return tuple(cols.call("eg_open_contest_data", cols.n, ncontest, nbytes, ids, c0, kappa, c1, c2, data, ok))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -328,7 +284,7 @@ def seal_contest_data_seeded(group: GroupContext, key: ElectionKey, man: AnyMani
     nc = man.n_contests
     bn = np.ascontiguousarray(ballot_nonces, dtype=np.uint8).reshape(-1, 32)
     nb = len(bn)
-    ids = _rows32(ballot_ids, nb, "ballot_ids")
+    ids = rows32(ballot_ids, nb, "ballot_ids")
     if not nb:
         w = np.asarray(data).shape[-1] if np.asarray(data).ndim else 0
         return SealedContestData(np.empty((0, nc, 512), np.uint8), np.empty((0, nc, w), np.uint8),
@@ -350,7 +306,7 @@ def open_contest_data_seeded(group: GroupContext, key: ElectionKey, man: AnyMani
     nc = man.n_contests
     bn = np.ascontiguousarray(ballot_nonces, dtype=np.uint8).reshape(-1, 32)
     nb = len(bn)
-    ids = _rows32(ballot_ids, nb, "ballot_ids")
+    ids = rows32(ballot_ids, nb, "ballot_ids")
     nbytes = sealed.nbytes
     if not nb:
         return np.zeros((0, nc, nbytes), np.uint8), np.zeros((0, nc), bool)

@@ -21,6 +21,7 @@ import numpy as np
 
 from . import native
 from .constants import P_BYTES, Q_BYTES, ProductionMode, constants_for
+from .marshal import ptr as _ptr
 
 BytesLike = Union[bytes, bytearray, memoryview]
 
@@ -50,10 +51,6 @@ def as_q_array(elems: Union[np.ndarray, Sequence["ElementModQ"], Sequence[int]])
     raw = bytearray().join(e.byteArray() if isinstance(e, ElementModQ) else int(e).to_bytes(Q_BYTES, "big")
                            for e in elems)
     return np.frombuffer(raw, dtype=np.uint8).reshape(-1, Q_BYTES)
-
-
-def _ptr(a: np.ndarray):
-    return a.ctypes.data_as(ctypes.c_void_p)
 
 
 def _p_be(x) -> bytes:

@@ -110,18 +110,10 @@ def _sig(lib: ctypes.CDLL) -> None:
         "eg_ctx_set_proof_format": ([P, I, I], I),
         "eg_fixed_base_create": ([P, P, I, ctypes.POINTER(c_vp)], I),
         "eg_fixed_base_destroy": ([P], I),
-        "eg_powp_batch": ([P, P, P, P, S], I),
-        "eg_fb_pow_batch": ([P, P, P, S], I),
-        "eg_powp_batch_dev": ([P, P, P, P, S], I),
-        "eg_fb_pow_batch_dev": ([P, P, P, S], I),
         "eg_multp_batch": ([P, P, P, P, S], I),
         "eg_prod_reduce": ([P, P, S, S, P], I),
         "eg_multinv_batch": ([P, P, P, S], I),
-        "eg_verify_ballots": ([P, P, P, S, S, S, S, U32, P, P, P, P, P, P, P], I),
         "eg_set_election_key": ([P, P, I], I),
-        "eg_verify_ballots_dev": ([P, P, P, S, S, S, S, U32, P, P, P, P, P, P, P], I),
-        "eg_encrypt_ballots": ([P, P, P, S, S, S, P, P, P, P, P, P], I),
-        "eg_encrypt_ballots_dev": ([P, P, P, S, S, S, P, P, P, P, P, P], I),
         "eg_ctx_set_ct_encrypt": ([P, I], I),
         "eg_ctx_set_coalescing": ([P, S, U32], I),
         "eg_powp_submit": ([P, P, P, P, ctypes.POINTER(c_vp)], I),
@@ -150,33 +142,28 @@ def _sig(lib: ctypes.CDLL) -> None:
         "eg_fb_pow_submit": ([P, P, P, ctypes.POINTER(c_vp)], I),
         "eg_fb_pow_one": ([P, P, P], I),
         "eg_ctx_set_ct_pow": ([P, I], I),
-        "eg_verify_ballots_manifest": ([P, P, P, S, S, U32P, U32P, U32P, P, P, P, P, P, P, P], I),
-        "eg_verify_ballots_manifest_dev": ([P, P, P, S, S, U32P, U32P, U32P, P, P, P, P, P, P, P], I),
-        "eg_encrypt_ballots_manifest": ([P, P, P, S, S, U32P, P, P, P, P, P, P], I),
-        "eg_encrypt_ballots_manifest_dev": ([P, P, P, S, S, U32P, P, P, P, P, P, P], I),
-        "eg_derive_ballot_nonces": ([P, S, S, U32P, P, P, P], I),
-        "eg_derive_ballot_nonces_dev": ([P, S, S, U32P, P, P, P], I),
-        "eg_ballot_hashes": ([P, S, S, U32P, P, P, P, P, P, P, P, P], I),
-        "eg_ballot_hashes_dev": ([P, S, S, U32P, P, P, P, P, P, P, P, P], I),
-        "eg_verify_code_chain": ([P, S, P, P, P, P, P], I),
-        "eg_verify_code_chain_dev": ([P, S, P, P, P, P, P], I),
-        "eg_derive_contest_data_nonces": ([P, S, S, P, P], I),
-        "eg_derive_contest_data_nonces_dev": ([P, S, S, P, P], I),
-        "eg_seal_contest_data": ([P, P, S, S, S, P, P, P, P, P, P], I),
-        "eg_seal_contest_data_dev": ([P, P, S, S, S, P, P, P, P, P, P], I),
-        "eg_open_contest_data": ([P, S, S, S, P, P, P, P, P, P, P], I),
-        "eg_open_contest_data_dev": ([P, S, S, S, P, P, P, P, P, P, P], I),
-        "eg_range_prove": ([P, P, P, S, U32, P, P, P, P, P], I),
-        "eg_range_prove_dev": ([P, P, P, S, U32, P, P, P, P, P], I),
-        "eg_range_verify": ([P, P, P, S, U32, P, P, P], I),
-        "eg_range_verify_dev": ([P, P, P, S, U32, P, P, P], I),
-        "eg_preencrypt_ballots": ([P, P, S, S, P, U32] + [P] * 11, I),
-        "eg_preencrypt_ballots_dev": ([P, P, S, S, P, U32] + [P] * 11, I),
-        "eg_preencrypt_record": ([P, P, S, S, P, P, U32] + [P] * 10, I),
-        "eg_preencrypt_record_dev": ([P, P, S, S, P, P, U32] + [P] * 10, I),
-        "eg_preencrypt_verify": ([P, S, S, P, P, U32] + [P] * 11, I),
-        "eg_preencrypt_verify_dev": ([P, S, S, P, P, U32] + [P] * 11, I),
     }
+    # declared once, bound twice: name takes host pointers, name_dev device pointers
+    pairs = {
+        "eg_powp_batch": ([P, P, P, P, S], I),
+        "eg_fb_pow_batch": ([P, P, P, S], I),
+        "eg_verify_ballots": ([P, P, P, S, S, S, S, U32, P, P, P, P, P, P, P], I),
+        "eg_encrypt_ballots": ([P, P, P, S, S, S, P, P, P, P, P, P], I),
+        "eg_verify_ballots_manifest": ([P, P, P, S, S, U32P, U32P, U32P, P, P, P, P, P, P, P], I),
+        "eg_encrypt_ballots_manifest": ([P, P, P, S, S, U32P, P, P, P, P, P, P], I),
+        "eg_derive_ballot_nonces": ([P, S, S, U32P, P, P, P], I),
+        "eg_ballot_hashes": ([P, S, S, U32P, P, P, P, P, P, P, P, P], I),
+        "eg_verify_code_chain": ([P, S, P, P, P, P, P], I),
+        "eg_derive_contest_data_nonces": ([P, S, S, P, P], I),
+        "eg_seal_contest_data": ([P, P, S, S, S, P, P, P, P, P, P], I),
+        "eg_open_contest_data": ([P, S, S, S, P, P, P, P, P, P, P], I),
+        "eg_range_prove": ([P, P, P, S, U32, P, P, P, P, P], I),
+        "eg_range_verify": ([P, P, P, S, U32, P, P, P], I),
+        "eg_preencrypt_ballots": ([P, P, S, S, P, U32] + [P] * 11, I),
+        "eg_preencrypt_record": ([P, P, S, S, P, P, U32] + [P] * 10, I),
+        "eg_preencrypt_verify": ([P, S, S, P, P, U32] + [P] * 11, I),
+    }
+    sigs.update({name + dev: sig for name, sig in pairs.items() for dev in ("", "_dev")})
     for name, (args, res) in sigs.items():
         fn = getattr(lib, name)
         fn.argtypes = args

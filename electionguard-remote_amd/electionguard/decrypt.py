@@ -21,7 +21,6 @@ selection, with every spoiled ballot's selections in ONE trustee batch per guard
 """
 from __future__ import annotations
 
-import ctypes
 import math
 import secrets
 from collections.abc import Sequence as _SequenceABC
@@ -34,6 +33,7 @@ import numpy as np
 from . import contest_data as _cd
 from .core import native
 from .core.group import GroupContext, as_p_array, as_q_array, p_bytes, q_bytes
+from .core.marshal import be_int as _be_int, ptr as _ptr
 from .keyceremony import GuardianKeys, backup_label, backup_open, poly_eval
 
 
@@ -165,10 +165,6 @@ def share_arrays(res) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
     return as_p_array([r.partialDecryption for r in res]), pr, rk
 
 
-def _ptr(a: np.ndarray):
-    return a.ctypes.data_as(ctypes.c_void_p)
-
-
 def _texts_array(texts) -> np.ndarray:
     """texts: (n, 2, 512) uint8 array or a sequence of (pad, data) int pairs."""
     if isinstance(texts, np.ndarray):
@@ -188,10 +184,6 @@ def _nonces(group: GroupContext, n: int, nonces) -> np.ndarray:
     for i, u in enumerate(nonces):
         a[i] = np.frombuffer(q_bytes(int(u)), dtype=np.uint8)
     return a
-
-
-def _be_int(row: np.ndarray) -> int:
-    return int.from_bytes(row.tobytes(), "big")
 
 
 def partial_decrypt_batch(group: GroupContext, secret: int, qbar: int, texts: np.ndarray,

@@ -36,12 +36,12 @@ from typing import List, Optional, Tuple
 
 import numpy as np
 
-from .ballot import (AnyManifest, ElectionKey, EncryptedBallots, _ptr, _u32p, batch_encryption,
-                     batch_encryption_device)
-from .codes import ManifestHashes, _b32, _call, _i, _q32, _rows32
+from .ballot import AnyManifest, ElectionKey, EncryptedBallots, batch_encryption, batch_encryption_device
+from .codes import ManifestHashes
 from .core import native
 from .core.group import DeviceBuffer, GroupContext
 from .core.hashing import hash_elems
+from .core.marshal import Columns, be32_row as _b32, be_int as _i, q_row, rows32, u32p
 
 MAX_SPC = 64           # EG_PRE_MAX_SPC
 CHUNK_CTS = 1 << 18    # EG_PRE_CHUNK_CTS: component ciphertexts per chunk
@@ -168,8 +168,8 @@ def hashes_from_cts_host(q: int, man: AnyManifest, code_bytes: int, hashes: Mani
     sh = pre_shape(man)
     cts = np.ascontiguousarray(vec_cts, dtype=np.uint8).reshape(-1, sh.V, 2, 512)
     nb = len(cts)
-    ids = _rows32(ballot_ids, nb, "ballot_ids")
-    dcon, mh = _rows32(hashes.dcon, sh.nc, "dcon"), _i(_q32(hashes.manifest_hash))
+    ids = rows32(ballot_ids, nb, "ballot_ids")
+    dcon, mh = rows32(hashes.dcon, sh.nc, "dcon"), _i(q_row(hashes.manifest_hash))
     srt = np.empty((nb, sh.nsel, 32), np.uint8)
     perm = np.empty((nb, sh.nsel), np.uint32)
     codes = np.empty((nb, sh.nsel), np.uint32)
@@ -212,9 +212,9 @@ def record_host(p: int, q: int, g: int, K: int, man: AnyManifest, code_bytes: in
     sh = pre_shape(man)
     votes = np.ascontiguousarray(votes, dtype=np.uint8).reshape(-1, sh.nsel)
     nb = len(votes)
-    bn = _rows32(ballot_nonces, nb, "ballot_nonces")
+    bn = rows32(ballot_nonces, nb, "ballot_nonces")
     srt = np.ascontiguousarray(sorted_hashes, dtype=np.uint8).reshape(nb, sh.nsel, 32)
-    dcon = _rows32(hashes.dcon, sh.nc, "dcon")
+    dcon = rows32(hashes.dcon, sh.nc, "dcon")
     sv = np.empty((nb, sh.S, 2, 512), np.uint8)
     rank = np.empty((nb, sh.T), np.uint32)
     codes = np.empty((nb, sh.T), np.uint32)
@@ -279,9 +279,9 @@ def verify_recorded_host(p: int, q: int, man: AnyManifest, code_bytes: int, hash
     codes = np.asarray(sel_codes, np.uint32).reshape(nb, sh.T)
     srt = np.ascontiguousarray(sorted_hashes, dtype=np.uint8).reshape(nb, sh.nsel, 32)
     cts = np.ascontiguousarray(cts, dtype=np.uint8).reshape(nb, sh.nsel, 2, 512)
-    cf = _rows32(conf, nb, "conf")
-    ids = _rows32(ballot_ids, nb, "ballot_ids")
-    dcon, mh = _rows32(hashes.dcon, sh.nc, "dcon"), _i(_q32(hashes.manifest_hash))
+    cf = rows32(conf, nb, "conf")
+    ids = rows32(ballot_ids, nb, "ballot_ids")
+    dcon, mh = rows32(hashes.dcon, sh.nc, "dcon"), _i(q_row(hashes.manifest_hash))
     okc = np.zeros((nb, sh.nc), bool)
     okb = np.zeros(nb, bool)
     for b in range(nb):
@@ -320,32 +320,13 @@ def preencrypt_ballots(group: GroupContext, key: ElectionKey, man: AnyManifest, 
     DeviceBuffers every field of the result is a DeviceBuffer (asynchronous on the context's stream)."""
     sh = pre_shape(man)
     nc, nsel = sh.nc, sh.nsel
-    spc = _u32(man.spc_list)
-    dcon, mh = _rows32(hashes.dcon, nc, "dcon"), np.ascontiguousarray(_q32(hashes.manifest_hash))
-    K = native.buf(key.K_be)
-    if isinstance(ballot_nonces, DeviceBuffer):
-        if not isinstance(ballot_ids, DeviceBuffer):
-            raise TypeError("device ballot nonces need device ballot ids")
-        nb = ballot_nonces.nbytes // 32
-        desc = group.to_device(np.concatenate([dcon.reshape(-1), mh]))
-        out = PreEncrypted(group.device_empty((nb, nsel, 32)), group.device_empty((nb, nsel), np.uint32),
-                           group.device_empty((nb, nsel), np.uint32), group.device_empty((nb,)),
-                           group.device_empty((nb, 32)), group.device_empty((nb, nc, 32)),
-                           group.device_empty((nb, sh.V, 2, 512)) if with_cts else None)
-        _call(group, "eg_preencrypt_ballots_dev", K, nb, nc, _u32p(spc), code_bytes, desc.ptr, desc.ptr + nc * 32,
-              ballot_ids.ptr, ballot_nonces.ptr, out.sorted.ptr, out.perm.ptr, out.codes.ptr, out.unique.ptr,
-              out.conf.ptr, out.chash.ptr, out.vec_cts.ptr if with_cts else None)
-        return out
-    bn = np.ascontiguousarray(ballot_nonces, dtype=np.uint8).reshape(-1, 32)
-    nb = len(bn)
-    ids = _rows32(ballot_ids, nb, "ballot_ids")
-    out = PreEncrypted(np.empty((nb, nsel, 32), np.uint8), np.empty((nb, nsel), np.uint32),
-                       np.empty((nb, nsel), np.uint32), np.empty(nb, np.uint8), np.empty((nb, 32), np.uint8),
-                       np.empty((nb, nc, 32), np.uint8), np.empty((nb, sh.V, 2, 512), np.uint8) if with_cts else None)
-    _call(group, "eg_preencrypt_ballots", K, nb, nc, _u32p(spc), code_bytes, _ptr(dcon), _ptr(mh), _ptr(ids), _ptr(bn),
-          _ptr(out.sorted), _ptr(out.perm), _ptr(out.codes), _ptr(out.unique), _ptr(out.conf), _ptr(out.chash),
-          _ptr(out.vec_cts) if with_cts else None)
-    return out
+    cols = Columns(group)
+    dcon, mh = cols.once(rows32(hashes.dcon, nc, "dcon")), cols.once(q_row(hashes.manifest_hash))
+    bn, ids = cols.item(ballot_nonces, (32,), "ballot_nonces"), cols.item(ballot_ids, (32,), "ballot_ids")
+    outs = [cols.out((nsel, 32)), cols.out((nsel,), np.uint32), cols.out((nsel,), np.uint32), cols.out(()),
+            cols.out((32,)), cols.out((nc, 32)), cols.out((sh.V, 2, 512), want=with_cts)]
+    return PreEncrypted(*cols.call("eg_preencrypt_ballots", native.buf(key.K_be), cols.n, nc, u32p(_u32(man.spc_list)),
+                                   code_bytes, dcon, mh, ids, bn, *outs))
 
 
 def record_parts(group: GroupContext, key: ElectionKey, man: AnyManifest, hashes: ManifestHashes, ballot_nonces,
@@ -353,32 +334,16 @@ def record_parts(group: GroupContext, key: ElectionKey, man: AnyManifest, hashes
     """eg_preencrypt_record[_dev]: the published parts and the encryptor's nonces (ballots is None)."""
     sh = pre_shape(man)
     nc, nsel = sh.nc, sh.nsel
-    spc, lim = _u32(man.spc_list), _u32(man.limits)
-    dcon = _rows32(hashes.dcon, nc, "dcon")
-    K = native.buf(key.K_be)
-    if isinstance(votes, DeviceBuffer):
-        if not (isinstance(ballot_nonces, DeviceBuffer) and isinstance(sorted_hashes, DeviceBuffer)):
-            raise TypeError("device votes need device ballot nonces and sorted hashes")
-        nb = votes.nbytes // nsel
-        d_dcon = group.to_device(dcon)
-        out = RecordedBallots(None, group.device_empty((nb, sh.S, 2, 512)), group.device_empty((nb, sh.T), np.uint32),
-                              group.device_empty((nb, sh.T), np.uint32), group.device_empty((nb, nc)), sorted_hashes,
-                              group.device_empty((nb, nsel, 4, 32)), group.device_empty((nb, nc, 32)))
-        _call(group, "eg_preencrypt_record_dev", K, nb, nc, _u32p(spc), _u32p(lim), code_bytes, d_dcon.ptr,
-              ballot_nonces.ptr, votes.ptr, sorted_hashes.ptr, out.sel_vecs.ptr, out.sel_rank.ptr, out.sel_codes.ptr,
-              out.sel_nonces.ptr, out.contest_nonces.ptr, out.ok.ptr)
-        return out
-    votes = np.ascontiguousarray(votes, dtype=np.uint8).reshape(-1, nsel)
-    nb = len(votes)
-    bn = _rows32(ballot_nonces, nb, "ballot_nonces")
-    srt = np.ascontiguousarray(sorted_hashes, dtype=np.uint8).reshape(nb, nsel, 32)
-    out = RecordedBallots(None, np.empty((nb, sh.S, 2, 512), np.uint8), np.empty((nb, sh.T), np.uint32),
-                          np.empty((nb, sh.T), np.uint32), np.empty((nb, nc), np.uint8), srt,
-                          np.empty((nb, nsel, 4, 32), np.uint8), np.empty((nb, nc, 32), np.uint8))
-    _call(group, "eg_preencrypt_record", K, nb, nc, _u32p(spc), _u32p(lim), code_bytes, _ptr(dcon), _ptr(bn),
-          _ptr(votes), _ptr(srt), _ptr(out.sel_vecs), _ptr(out.sel_rank), _ptr(out.sel_codes), _ptr(out.sel_nonces),
-          _ptr(out.contest_nonces), _ptr(out.ok))
-    return out
+    cols = Columns(group)
+    dcon = cols.once(rows32(hashes.dcon, nc, "dcon"))
+    votes = cols.item(votes, (nsel,), "votes")
+    bn, srt = cols.item(ballot_nonces, (32,), "ballot_nonces"), cols.item(sorted_hashes, (nsel, 32), "sorted_hashes")
+    sv, rank, codes = cols.out((sh.S, 2, 512)), cols.out((sh.T,), np.uint32), cols.out((sh.T,), np.uint32)
+    sn, cn, ok = cols.out((nsel, 4, 32)), cols.out((nc, 32)), cols.out((nc,))
+    sv, rank, codes, sn, cn, ok = cols.call(
+        "eg_preencrypt_record", native.buf(key.K_be), cols.n, nc, u32p(_u32(man.spc_list)), u32p(_u32(man.limits)),
+        code_bytes, dcon, bn, votes, srt, sv, rank, codes, sn, cn, ok)
+    return RecordedBallots(None, sv, rank, codes, ok, srt.value, sn, cn)
 
 
 def record_ballots(group: GroupContext, key: ElectionKey, qbar: int, man: AnyManifest, hashes: ManifestHashes,
@@ -407,27 +372,13 @@ def verify_recorded(group: GroupContext, man: AnyManifest, hashes: ManifestHashe
     DeviceBuffers for every array -> two DeviceBuffers of flag bytes, asynchronous."""
     sh = pre_shape(man)
     nc, nsel = sh.nc, sh.nsel
-    spc, lim = _u32(man.spc_list), _u32(man.limits)
-    dcon, mh = _rows32(hashes.dcon, nc, "dcon"), np.ascontiguousarray(_q32(hashes.manifest_hash))
-    if isinstance(sel_vecs, DeviceBuffer):
-        nb = conf.nbytes // 32
-        desc = group.to_device(np.concatenate([dcon.reshape(-1), mh]))
-        okc, okb = group.device_empty((nb, nc)), group.device_empty((nb,))
-        _call(group, "eg_preencrypt_verify_dev", nb, nc, _u32p(spc), _u32p(lim), code_bytes, desc.ptr,
-              desc.ptr + nc * 32, ballot_ids.ptr, sel_vecs.ptr, sel_rank.ptr, sel_codes.ptr, sorted_hashes.ptr, cts.ptr,
-              conf.ptr, okc.ptr, okb.ptr)
-        return okc, okb
-    cf = np.ascontiguousarray(conf, dtype=np.uint8).reshape(-1, 32)
-    nb = len(cf)
-    ids = _rows32(ballot_ids, nb, "ballot_ids")
-    sv = np.ascontiguousarray(sel_vecs, dtype=np.uint8)
-    srt = np.ascontiguousarray(sorted_hashes, dtype=np.uint8)
-    ct = np.ascontiguousarray(cts, dtype=np.uint8)
-    rk, cd = _u32(sel_rank), _u32(sel_codes)
-    if sv.size != nb * sh.S * 1024 or srt.size != nb * nsel * 32 or ct.size != nb * nsel * 1024 or \
-            rk.size != nb * sh.T or cd.size != nb * sh.T:
-        raise ValueError("verify_recorded: array sizes do not match the manifest")
-    okc, okb = np.zeros((nb, nc), np.uint8), np.zeros(nb, np.uint8)
-    _call(group, "eg_preencrypt_verify", nb, nc, _u32p(spc), _u32p(lim), code_bytes, _ptr(dcon), _ptr(mh), _ptr(ids),
-          _ptr(sv), _ptr(rk), _ptr(cd), _ptr(srt), _ptr(ct), _ptr(cf), _ptr(okc), _ptr(okb))
-    return okc.astype(bool), okb.astype(bool)
+    cols = Columns(group)
+    dcon, mh = cols.once(rows32(hashes.dcon, nc, "dcon")), cols.once(q_row(hashes.manifest_hash))
+    cf, ids = cols.item(conf, (32,), "conf"), cols.item(ballot_ids, (32,), "ballot_ids")
+    sv = cols.item(sel_vecs, (sh.S, 2, 512), "sel_vecs")
+    rk = cols.item(sel_rank, (sh.T,), "sel_rank", np.uint32)
+    cd = cols.item(sel_codes, (sh.T,), "sel_codes", np.uint32)
+    srt, ct = cols.item(sorted_hashes, (nsel, 32), "sorted_hashes"), cols.item(cts, (nsel, 2, 512), "cts")
+    okc, okb = cols.out((nc,), flag=True), cols.out((), flag=True)
+    return tuple(cols.call("eg_preencrypt_verify", cols.n, nc, u32p(_u32(man.spc_list)), u32p(_u32(man.limits)),
+                           code_bytes, dcon, mh, ids, sv, rk, cd, srt, ct, cf, okc, okb))

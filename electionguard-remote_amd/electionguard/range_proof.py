@@ -33,6 +33,7 @@ import numpy as np
 
 from .core import native
 from .core.hashing import hash_elems
+from .core.marshal import Columns, be32, be_int as _i
 
 MAX_LIMIT = 15   # EG_RANGE_MAX_LIMIT
 CHUNK_JOBS = 1 << 16   # kRangeChunkJobs (csrc/eg_capi_range.inc)
@@ -62,10 +63,6 @@ def _limit(limit: int) -> int:
 
 def _key_int(key) -> int:
     return int(key.K) if hasattr(key, "K") else int(key)
-
-
-def _i(row) -> int:
-    return int.from_bytes(bytes(row), "big")
 
 
 # ---------------------------------------------------------------------------------------------
@@ -174,24 +171,6 @@ def verify_host(group, key, qbar: int, limit: int, cts, proofs) -> np.ndarray:
 # ---------------------------------------------------------------------------------------------
 # GPU calls (numpy arrays through the host entry points, DeviceBuffers through the _dev ones)
 # ---------------------------------------------------------------------------------------------
-def _q32(x: int) -> bytes:
-    return int(x).to_bytes(32, "big")
-
-
-def _ptr(a: np.ndarray):
-    import ctypes
-    return a.ctypes.data_as(ctypes.c_void_p)
-
-
-def _call(group, name: str, *args) -> None:
-    native.check(group._lib, name, getattr(group._lib, name)(group.handle, *args))
-
-
-def _is_dev(x) -> bool:
-    from .core.group import DeviceBuffer
-    return isinstance(x, DeviceBuffer)
-
-
 def prove(group, key, qbar: int, limit: int, cts, values, R, nonces):
     """-> proofs (n, L+1, 2, 32) for cts (n, 2, 512), values (n,) in 0..L, R (n, 32) and nonces
     (n, 2L+3, 32).  With DeviceBuffers for all four the result is a DeviceBuffer (asynchronous on
@@ -199,50 +178,22 @@ def prove(group, key, qbar: int, limit: int, cts, values, R, nonces):
     rejects; with arrays such a value raises EgError naming the item.  group.ct_encrypt makes the
     fixed-base reads masked scans (same bytes)."""
     L = _limit(limit)
-    K, qb = native.buf(key.K_be), native.buf(_q32(qbar))
-    if _is_dev(cts):
-        if not all(_is_dev(x) for x in (values, R, nonces)):
-            raise TypeError("device ciphertexts need device values, R and nonces")
-        n = cts.nbytes // 1024
-        if values.nbytes != n or R.nbytes != n * 32 or nonces.nbytes != n * (2 * L + 3) * 32:
-            raise ValueError(f"expected {n} values, {n} R and {n} x {2 * L + 3} nonces")
-        proofs = group.device_empty((n, L + 1, 2, 32))
-        _call(group, "eg_range_prove_dev", K, qb, n, L, cts.ptr, values.ptr, R.ptr, nonces.ptr, proofs.ptr)
-        return proofs
-    cts = np.ascontiguousarray(cts, dtype=np.uint8).reshape(-1, 2, 512)
-    n = len(cts)
-    values = np.ascontiguousarray(values, dtype=np.uint8).reshape(-1)
-    R = np.ascontiguousarray(R, dtype=np.uint8).reshape(-1, 32)
-    nonces = np.ascontiguousarray(nonces, dtype=np.uint8).reshape(-1, 2 * L + 3, 32)
-    if len(values) != n or len(R) != n or len(nonces) != n:
-        raise ValueError(f"expected {n} values, {n} R and {n} x {2 * L + 3} nonces")
-    proofs = np.zeros((n, L + 1, 2, 32), np.uint8)
-    _call(group, "eg_range_prove", K, qb, n, L, _ptr(cts), _ptr(values), _ptr(R), _ptr(nonces), _ptr(proofs))
-    return proofs
+    cols = Columns(group)
+    cts = cols.item(cts, (2, 512), "cts")
+    values, R = cols.item(values, (), "values"), cols.item(R, (32,), "R")
+    nonces = cols.item(nonces, (2 * L + 3, 32), "nonces")
+    return cols.call("eg_range_prove", native.buf(key.K_be), native.buf(be32(qbar)), cols.n, L, cts, values, R,
+                     nonces, cols.out((L + 1, 2, 32)))[0]
 
 
 def verify(group, key, qbar: int, limit: int, cts, proofs):
     """-> ok (n,) bool for cts (n, 2, 512) and proofs (n, L+1, 2, 32); DeviceBuffers in, a
     DeviceBuffer of flag bytes out (asynchronous)."""
     L = _limit(limit)
-    K, qb = native.buf(key.K_be), native.buf(_q32(qbar))
-    if _is_dev(cts):
-        if not _is_dev(proofs):
-            raise TypeError("device ciphertexts need device proofs")
-        n = cts.nbytes // 1024
-        if proofs.nbytes != n * (L + 1) * 64:
-            raise ValueError(f"expected {n} proofs of {L + 1} branches")
-        ok = group.device_empty((n,))
-        _call(group, "eg_range_verify_dev", K, qb, n, L, cts.ptr, proofs.ptr, ok.ptr)
-        return ok
-    cts = np.ascontiguousarray(cts, dtype=np.uint8).reshape(-1, 2, 512)
-    n = len(cts)
-    proofs = np.ascontiguousarray(proofs, dtype=np.uint8)
-    if proofs.size != n * (L + 1) * 64:
-        raise ValueError(f"expected {n} proofs of {L + 1} branches")
-    ok = np.zeros(n, np.uint8)
-    _call(group, "eg_range_verify", K, qb, n, L, _ptr(cts), _ptr(proofs), _ptr(ok))
-    return ok.astype(bool)
+    cols = Columns(group)
+    cts, proofs = cols.item(cts, (2, 512), "cts"), cols.item(proofs, (L + 1, 2, 32), "proofs")
+    return cols.call("eg_range_verify", native.buf(key.K_be), native.buf(be32(qbar)), cols.n, L, cts, proofs,
+                     cols.out((), flag=True))[0]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -287,7 +238,7 @@ def contest_limit_prove(group, key, qbar: int, man, eb, votes, sel_nonces, nonce
         values[:, k] = votes[:, o:o + c.n_selections].sum(axis=1)
         for b in range(nb):
             r = sum(_i(sn[b, o + s, 0]) for s in range(c.n_selections)) % group.q
-            rsum[b, k] = np.frombuffer(_q32(r), np.uint8)
+            rsum[b, k] = np.frombuffer(be32(r), np.uint8)
     out = np.zeros((nb, nc, Lmax + 1, 2, 32), np.uint8)
     limits = np.array([_limit(c.votes_allowed) for c in man.contests])
     for L in np.unique(limits):

@@ -38,8 +38,9 @@ def main():
     a = ap.parse_args()
 
     from electionguard import codes as C
-    from electionguard.ballot import ElectionKey, Manifest, Verifier, _u32p, batch_encryption_device, random_votes
+    from electionguard.ballot import ElectionKey, Manifest, Verifier, batch_encryption_device, random_votes
     from electionguard.core import native, productionGroup
+    from electionguard.core.marshal import u32p
     from electionguard.keyceremony import key_ceremony
 
     group = productionGroup(0)
@@ -61,7 +62,7 @@ def main():
     d_B = group.device_empty((nb, 32))
     d_oks, d_okc, d_tal = group.device_buffer(nb * nsel), group.device_buffer(nb * nc), \
         group.device_buffer(man.n_real * 2 * 512)
-    spc = _u32p(man.spc_list)
+    spc = u32p(man.spc_list)
     V = Verifier(group, key, qbar, man)
 
     def nonces():
