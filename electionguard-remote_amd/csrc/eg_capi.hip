@@ -34,11 +34,13 @@
 #include "../../include/eg_hip_contestdata.h"
 #include "../../include/eg_hip_range.h"
 #include "../../include/eg_hip_preencrypt.h"
+#include "../../include/eg_hip_ballot2.h"
 #include "eg_kernels.hpp"
 #include "eg_codes.hpp"
 #include "eg_hmac.hpp"
 #include "eg_range.hpp"
 #include "eg_preencrypt.hpp"
+#include "eg_ballot2.hpp"
 #include "eg_pow16.h"
 #include "eg_stage.hpp"
 
@@ -169,7 +171,13 @@ constexpr int kCtEncWindow = 6;
 
 enum Slot {
   W_IN0, W_IN1, W_EXP, W_OUT, W_E0, W_E1, W_E2, W_E3, W_JOBS, W_SCR, W_TMP, W_FLAGS, W_SCAL,
-  W_BE0, W_BE1, W_BE2, W_OK0, W_OK1, W_OFF, W_H0, W_H1, W_H2, W_H3, W_H4, W_H5, W_H6, W_H7, W_H8, W_EB0, W_EB1, W_EB2, W_EA2, W_YA, W_YB, W_RZ, W_CRF, W_CAST, W_ANY, W_GATHER, W_KBE, W_STAGE, W_NSLOT
+  W_BE0, W_BE1, W_BE2, W_OK0, W_OK1, W_OFF, W_H0, W_H1, W_H2, W_H3, W_H4, W_H5, W_H6, W_H7, W_H8, W_EB0, W_EB1, W_EB2, W_EA2, W_YA, W_YB, W_RZ, W_CRF, W_CAST, W_ANY, W_GATHER, W_KBE, W_STAGE,
+  // eg_capi_ballot2.inc's own (its chunks call the range chunk functions, whose slots stay theirs):
+  // imported ciphertexts and their range flags, aggregates and their bytes, the limit classes' packed
+  // ciphertexts / proofs / one byte per item / R / nonce rows, per-selection flags, one byte per
+  // contest, the ciphertext jobs' scalars, the contests' nonce sums, the tally and its bytes
+  W_B2_E, W_B2_LT, W_B2_AGG, W_B2_AGGBE, W_B2_CTS, W_B2_PRF, W_B2_OK, W_B2_R, W_B2_NON, W_B2_FL, W_B2_OKC, W_B2_SC,
+  W_B2_RSUM, W_B2_TALLY, W_B2_TBE, W_NSLOT
 };
 
 struct eg_ctx {
@@ -1293,6 +1301,7 @@ extern "C" int eg_ctx_profile_end(eg_ctx* c, double* ms, double* mm, double* sqr
 #include "eg_capi_codes.inc"
 #include "eg_capi_contestdata.inc"
 #include "eg_capi_range.inc"
+#include "eg_capi_ballot2.inc"
 #include "eg_capi_preencrypt.inc"
 #include "eg_capi_coalesce.inc"
 #include "eg_capi_comm.inc"

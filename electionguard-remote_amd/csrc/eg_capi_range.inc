@@ -101,7 +101,10 @@ static int range_verify_chunk_locked(eg_ctx* c, size_t n, uint32_t L, const uint
     T.S = XB; T.jobs = jv[3]; T.njobs = nx; T.ygat = YB;
     if ((rc = launch_pow(c, XA, jv[2], nx, E, SC, COMM, G, K, nullptr, YA, &T))) return rc;
   }
-  // alpha^q == 1 and beta^q == 1 fold into the range flags
+  // alpha^q == 1 and beta^q == 1 fold into the range flags.  From here on LTP (W_FLAGS) holds, for
+  // item i of this call, its alpha's flag at [2 i] and its beta's at [2 i + 1]: range (k_import)
+  // AND residue.  b2_verify_chunk_locked (eg_capi_ballot2.inc) reads them there after this
+  // function returns and before its next call, for the contests' verdicts: keep the slot and layout.
   LAUNCH_F(c, k_resid_check, dim3(grid_for(n)), c->d, RZ, (uint32_t)n, LTP, 2u);
   LAUNCH_F(c, k_resid_check, dim3(grid_for(n)), c->d, RZ + n * 2 * kW, (uint32_t)n, LTP + 1, 2u);
   HIPCHK(hipGetLastError());

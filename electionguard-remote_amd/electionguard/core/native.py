@@ -71,6 +71,13 @@ EXPORTED_PREENCRYPT = [
 ]
 
 
+# Every symbol declared in include/eg_hip_ballot2.h (ballots without placeholder selections).
+EXPORTED_BALLOT2 = [
+    "eg_encrypt_ballots_v2", "eg_encrypt_ballots_v2_dev",
+    "eg_verify_ballots_v2", "eg_verify_ballots_v2_dev",
+]
+
+
 class NativeUnavailable(RuntimeError):
     pass
 
@@ -162,6 +169,8 @@ def _sig(lib: ctypes.CDLL) -> None:
         "eg_preencrypt_ballots": ([P, P, S, S, P, U32] + [P] * 11, I),
         "eg_preencrypt_record": ([P, P, S, S, P, P, U32] + [P] * 10, I),
         "eg_preencrypt_verify": ([P, S, S, P, P, U32] + [P] * 11, I),
+        "eg_encrypt_ballots_v2": ([P, P, P, S, S, U32P, U32P, U32P] + [P] * 6, I),
+        "eg_verify_ballots_v2": ([P, P, P, S, S, U32P, U32P, U32P] + [P] * 7, I),
     }
     sigs.update({name + dev: sig for name, sig in pairs.items() for dev in ("", "_dev")})
     for name, (args, res) in sigs.items():

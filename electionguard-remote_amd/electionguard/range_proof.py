@@ -22,7 +22,10 @@ R (n, 32), nonces (n, 2L+3, 32), ok (n,).
 ``prove_host`` / ``verify_host`` restate the definitions on CPython ints and never call the GPU;
 ``prove`` / ``verify`` run on the GPU (csrc/eg_range.hpp and the k_pow jobs of
 csrc/eg_capi_range.inc) on numpy arrays or DeviceBuffers; ``contest_limit_prove`` /
-``contest_limit_verify`` put a 0..votes_allowed proof on every contest's aggregate.
+``contest_limit_verify`` put a 0..votes_allowed proof on every contest's aggregate, composed on the
+host from numpy arrays.  Whole ballots of that form (no placeholders, a range proof per selection
+and per contest) are encrypted, verified and tallied in one batch call by ``ballot2``
+(include/eg_hip_ballot2.h), which also takes device-resident ballots.
 """
 from __future__ import annotations
 
@@ -225,7 +228,8 @@ def contest_limit_prove(group, key, qbar: int, man, eb, votes, sel_nonces, nonce
     batch_encryption (the aggregate's nonce is the sum of the selections' R mod q); nonces
     (nb, nc, 2 Lmax + 3, 32), contest k reading its first 2 L_k + 3 rows, Lmax =
     man.max_votes_allowed.  -> proofs (nb, nc, Lmax + 1, 2, 32), contest k's first L_k + 1 branches
-    filled and the rest zero.  Contests are grouped by limit, one prove() call per limit."""
+    filled and the rest zero.  Contests are grouped by limit, one prove() call per limit.
+    ballot2.encrypt makes whole placeholder-free ballots, these proofs included, in one batch call."""
     nb, nc, Lmax = eb.n, man.n_contests, _limit(man.max_votes_allowed)
     cts = np.ascontiguousarray(eb.cts, dtype=np.uint8).reshape(nb, man.nsel, 2, 512)
     votes = np.ascontiguousarray(votes, dtype=np.uint8).reshape(nb, man.nsel)
@@ -255,7 +259,9 @@ def contest_limit_verify(group, key, qbar: int, man, eb, proofs) -> np.ndarray:
 
     For manifests whose ballots set no placeholders this supersedes the fused verifier's
     ok_contest (the constant proof of the padded sum, which an undervoted contest cannot pass);
-    ok_sel and the tally still come from Verifier.verify on the same ballots."""
+    ok_sel and the tally still come from Verifier.verify on the same ballots.  Ballots made
+    without placeholders from the start are verified and tallied in one batch call, device-resident
+    ones included, by ballot2.Verifier2 (include/eg_hip_ballot2.h)."""
     nb, nc, Lmax = eb.n, man.n_contests, _limit(man.max_votes_allowed)
     cts = np.ascontiguousarray(eb.cts, dtype=np.uint8).reshape(nb, man.nsel, 2, 512)
     proofs = np.ascontiguousarray(proofs, dtype=np.uint8).reshape(nb, nc, Lmax + 1, 2, 32)
