@@ -35,12 +35,14 @@
 #include "../../include/eg_hip_range.h"
 #include "../../include/eg_hip_preencrypt.h"
 #include "../../include/eg_hip_ballot2.h"
+#include "../../include/eg_hip_codes2.h"
 #include "eg_kernels.hpp"
 #include "eg_codes.hpp"
 #include "eg_hmac.hpp"
 #include "eg_range.hpp"
 #include "eg_preencrypt.hpp"
 #include "eg_ballot2.hpp"
+#include "eg_codes2.hpp"
 #include "eg_pow16.h"
 #include "eg_stage.hpp"
 
@@ -177,7 +179,9 @@ enum Slot {
   // ciphertexts / proofs / one byte per item / R / nonce rows, per-selection flags, one byte per
   // contest, the ciphertext jobs' scalars, the contests' nonce sums, the tally and its bytes
   W_B2_E, W_B2_LT, W_B2_AGG, W_B2_AGGBE, W_B2_CTS, W_B2_PRF, W_B2_OK, W_B2_R, W_B2_NON, W_B2_FL, W_B2_OKC, W_B2_SC,
-  W_B2_RSUM, W_B2_TALLY, W_B2_TBE, W_NSLOT
+  W_B2_RSUM, W_B2_TALLY, W_B2_TBE,
+  // eg_capi_codes2.inc's opening: R per selection, the bytes of g^R and of K^R
+  W_C2_R, W_C2_GR, W_C2_KR, W_NSLOT
 };
 
 struct eg_ctx {
@@ -1302,6 +1306,7 @@ extern "C" int eg_ctx_profile_end(eg_ctx* c, double* ms, double* mm, double* sqr
 #include "eg_capi_contestdata.inc"
 #include "eg_capi_range.inc"
 #include "eg_capi_ballot2.inc"
+#include "eg_capi_codes2.inc"
 #include "eg_capi_preencrypt.inc"
 #include "eg_capi_coalesce.inc"
 #include "eg_capi_comm.inc"

@@ -78,6 +78,13 @@ EXPORTED_BALLOT2 = [
 ]
 
 
+# Every symbol declared in include/eg_hip_codes2.h (seeded nonces and opening of those ballots).
+EXPORTED_CODES2 = [
+    "eg_derive_ballot_nonces_v2", "eg_derive_ballot_nonces_v2_dev",
+    "eg_open_ballots_v2", "eg_open_ballots_v2_dev",
+]
+
+
 class NativeUnavailable(RuntimeError):
     pass
 
@@ -171,6 +178,8 @@ def _sig(lib: ctypes.CDLL) -> None:
         "eg_preencrypt_verify": ([P, S, S, P, P, U32] + [P] * 11, I),
         "eg_encrypt_ballots_v2": ([P, P, P, S, S, U32P, U32P, U32P] + [P] * 6, I),
         "eg_verify_ballots_v2": ([P, P, P, S, S, U32P, U32P, U32P] + [P] * 7, I),
+        "eg_derive_ballot_nonces_v2": ([P, S, S, U32P, U32P, U32P, P, P, P], I),
+        "eg_open_ballots_v2": ([P, P, S, S, U32P, U32P, U32P, P, P, P, P], I),
     }
     sigs.update({name + dev: sig for name, sig in pairs.items() for dev in ("", "_dev")})
     for name, (args, res) in sigs.items():
