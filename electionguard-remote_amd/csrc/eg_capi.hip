@@ -36,6 +36,7 @@
 #include "../../include/eg_hip_preencrypt.h"
 #include "../../include/eg_hip_ballot2.h"
 #include "../../include/eg_hip_codes2.h"
+#include "../../include/eg_hip_prodpow.h"
 #include "eg_kernels.hpp"
 #include "eg_codes.hpp"
 #include "eg_hmac.hpp"
@@ -43,6 +44,7 @@
 #include "eg_preencrypt.hpp"
 #include "eg_ballot2.hpp"
 #include "eg_codes2.hpp"
+#include "eg_prodpow.hpp"
 #include "eg_pow16.h"
 #include "eg_stage.hpp"
 
@@ -181,7 +183,10 @@ enum Slot {
   W_B2_E, W_B2_LT, W_B2_AGG, W_B2_AGGBE, W_B2_CTS, W_B2_PRF, W_B2_OK, W_B2_R, W_B2_NON, W_B2_FL, W_B2_OKC, W_B2_SC,
   W_B2_RSUM, W_B2_TALLY, W_B2_TBE,
   // eg_capi_codes2.inc's opening: R per selection, the bytes of g^R and of K^R
-  W_C2_R, W_C2_GR, W_C2_KR, W_NSLOT
+  W_C2_R, W_C2_GR, W_C2_KR,
+  // eg_capi_prodpow.inc's own: imported terms or power tables, the sort arrays, segment products (then
+  // the bit products' partial runs), bucket products, bit products, the rows' accumulators
+  W_PP_E, W_PP_SORT, W_PP_PART, W_PP_BK, W_PP_Q, W_PP_ACC, W_NSLOT
 };
 
 struct eg_ctx {
@@ -1310,6 +1315,7 @@ extern "C" int eg_ctx_profile_end(eg_ctx* c, double* ms, double* mm, double* sqr
 #include "eg_capi_preencrypt.inc"
 #include "eg_capi_coalesce.inc"
 #include "eg_capi_comm.inc"
+#include "eg_capi_prodpow.inc"
 
 // ------------------------------------------------------------------------------
 // device-pointer powP / fixed-base powP (asynchronous on the ctx stream): the

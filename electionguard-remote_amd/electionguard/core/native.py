@@ -84,6 +84,11 @@ EXPORTED_CODES2 = [
     "eg_open_ballots_v2", "eg_open_ballots_v2_dev",
 ]
 
+# Every symbol declared in include/eg_hip_prodpow.h (products of powers over one shared exponent vector).
+EXPORTED_PRODPOW = [
+    "eg_prod_pow", "eg_prod_pow_dev", "eg_prod_pow_plan",
+]
+
 
 class NativeUnavailable(RuntimeError):
     pass
@@ -156,6 +161,7 @@ def _sig(lib: ctypes.CDLL) -> None:
         "eg_fb_pow_submit": ([P, P, P, ctypes.POINTER(c_vp)], I),
         "eg_fb_pow_one": ([P, P, P], I),
         "eg_ctx_set_ct_pow": ([P, I], I),
+        "eg_prod_pow_plan": ([S, S, I, I, ctypes.POINTER(I), ctypes.POINTER(I), D], I),
     }
     # declared once, bound twice: name takes host pointers, name_dev device pointers
     pairs = {
@@ -180,6 +186,7 @@ def _sig(lib: ctypes.CDLL) -> None:
         "eg_verify_ballots_v2": ([P, P, P, S, S, U32P, U32P, U32P] + [P] * 7, I),
         "eg_derive_ballot_nonces_v2": ([P, S, S, U32P, U32P, U32P, P, P, P], I),
         "eg_open_ballots_v2": ([P, P, S, S, U32P, U32P, U32P, P, P, P, P], I),
+        "eg_prod_pow": ([P, P, S, S, P, S, S, I, I, P], I),
     }
     sigs.update({name + dev: sig for name, sig in pairs.items() for dev in ("", "_dev")})
     for name, (args, res) in sigs.items():
