@@ -37,6 +37,7 @@
 #include "../../include/eg_hip_ballot2.h"
 #include "../../include/eg_hip_codes2.h"
 #include "../../include/eg_hip_prodpow.h"
+#include "../../include/eg_hip_decrypt2.h"
 #include "eg_kernels.hpp"
 #include "eg_codes.hpp"
 #include "eg_hmac.hpp"
@@ -45,6 +46,7 @@
 #include "eg_ballot2.hpp"
 #include "eg_codes2.hpp"
 #include "eg_prodpow.hpp"
+#include "eg_decrypt2.hpp"
 #include "eg_pow16.h"
 #include "eg_stage.hpp"
 
@@ -186,7 +188,9 @@ enum Slot {
   W_C2_R, W_C2_GR, W_C2_KR,
   // eg_capi_prodpow.inc's own: imported terms or power tables, the sort arrays, segment products (then
   // the bit products' partial runs), bucket products, bit products, the rows' accumulators
-  W_PP_E, W_PP_SORT, W_PP_PART, W_PP_BK, W_PP_Q, W_PP_ACC, W_NSLOT
+  W_PP_E, W_PP_SORT, W_PP_PART, W_PP_BK, W_PP_Q, W_PP_ACC,
+  // eg_capi_decrypt2.inc's own: the constants of a call (the tag, K, then the weights or the share keys)
+  W_D2_CONST, W_NSLOT
 };
 
 struct eg_ctx {
@@ -1316,6 +1320,7 @@ extern "C" int eg_ctx_profile_end(eg_ctx* c, double* ms, double* mm, double* sqr
 #include "eg_capi_coalesce.inc"
 #include "eg_capi_comm.inc"
 #include "eg_capi_prodpow.inc"
+#include "eg_capi_decrypt2.inc"
 
 // ------------------------------------------------------------------------------
 // device-pointer powP / fixed-base powP (asynchronous on the ctx stream): the

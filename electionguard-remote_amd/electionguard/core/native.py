@@ -89,6 +89,14 @@ EXPORTED_PRODPOW = [
     "eg_prod_pow", "eg_prod_pow_dev", "eg_prod_pow_plan",
 ]
 
+# Every symbol declared in include/eg_hip_decrypt2.h (threshold decryption with one combined proof per text).
+EXPORTED_DECRYPT2 = [
+    "eg_decrypt2_commit", "eg_decrypt2_respond",
+    "eg_decrypt2_combine", "eg_decrypt2_combine_dev",
+    "eg_decrypt2_check", "eg_decrypt2_check_dev",
+    "eg_decrypt2_verify", "eg_decrypt2_verify_dev",
+]
+
 
 class NativeUnavailable(RuntimeError):
     pass
@@ -162,6 +170,8 @@ def _sig(lib: ctypes.CDLL) -> None:
         "eg_fb_pow_one": ([P, P, P], I),
         "eg_ctx_set_ct_pow": ([P, I], I),
         "eg_prod_pow_plan": ([S, S, I, I, ctypes.POINTER(I), ctypes.POINTER(I), D], I),
+        "eg_decrypt2_commit": ([P, P, P, P, S, P, P, P], I),
+        "eg_decrypt2_respond": ([P, P, P, P, S, P], I),
     }
     # declared once, bound twice: name takes host pointers, name_dev device pointers
     pairs = {
@@ -187,6 +197,9 @@ def _sig(lib: ctypes.CDLL) -> None:
         "eg_derive_ballot_nonces_v2": ([P, S, S, U32P, U32P, U32P, P, P, P], I),
         "eg_open_ballots_v2": ([P, P, S, S, U32P, U32P, U32P, P, P, P, P], I),
         "eg_prod_pow": ([P, P, S, S, P, S, S, I, I, P], I),
+        "eg_decrypt2_combine": ([P, P, P, S, S, P, P, P, P, P, P, P], I),
+        "eg_decrypt2_check": ([P, S, S, P, P, P, P, P, P, P, P], I),
+        "eg_decrypt2_verify": ([P, P, P, S, P, P, P, P], I),
     }
     sigs.update({name + dev: sig for name, sig in pairs.items() for dev in ("", "_dev")})
     for name, (args, res) in sigs.items():
