@@ -38,6 +38,7 @@
 #include "../../include/eg_hip_codes2.h"
 #include "../../include/eg_hip_prodpow.h"
 #include "../../include/eg_hip_decrypt2.h"
+#include "../../include/eg_hip_shuffle.h"
 #include "eg_kernels.hpp"
 #include "eg_codes.hpp"
 #include "eg_hmac.hpp"
@@ -47,6 +48,7 @@
 #include "eg_codes2.hpp"
 #include "eg_prodpow.hpp"
 #include "eg_decrypt2.hpp"
+#include "eg_shuffle.hpp"
 #include "eg_pow16.h"
 #include "eg_stage.hpp"
 
@@ -190,7 +192,15 @@ enum Slot {
   // the bit products' partial runs), bucket products, bit products, the rows' accumulators
   W_PP_E, W_PP_SORT, W_PP_PART, W_PP_BK, W_PP_Q, W_PP_ACC,
   // eg_capi_decrypt2.inc's own: the constants of a call (the tag, K, then the weights or the share keys)
-  W_D2_CONST, W_NSLOT
+  W_D2_CONST,
+  // eg_capi_shuffle.inc's own: the constants of a call (gseed, cof or the tags and K, the flag word),
+  // big-endian rows in and out, imported elements, powers and products, scalars, the job table, a host
+  // mix's psi; the proof's: r mod q, psi's inverse, hash levels, dot and scan levels, the chain, the
+  // that values, the commitments, their bytes (twice), a host call's arrays, < p flags, the verifier's
+  // imported and derived elements
+  W_SH_CONST, W_SH_X, W_SH_E, W_SH_O, W_SH_SC, W_SH_JOBS, W_SH_PSI,
+  W_SH_R, W_SH_PSI2, W_SH_H, W_SH_D, W_SH_T, W_SH_O2, W_SH_O3, W_SH_TX, W_SH_BE, W_SH_BE2, W_SH_IO, W_SH_LT, W_SH_V,
+  W_SH_W, W_NSLOT
 };
 
 struct eg_ctx {
@@ -1321,6 +1331,7 @@ extern "C" int eg_ctx_profile_end(eg_ctx* c, double* ms, double* mm, double* sqr
 #include "eg_capi_comm.inc"
 #include "eg_capi_prodpow.inc"
 #include "eg_capi_decrypt2.inc"
+#include "eg_capi_shuffle.inc"
 
 // ------------------------------------------------------------------------------
 // device-pointer powP / fixed-base powP (asynchronous on the ctx stream): the

@@ -97,6 +97,14 @@ EXPORTED_DECRYPT2 = [
     "eg_decrypt2_verify", "eg_decrypt2_verify_dev",
 ]
 
+# Every symbol declared in include/eg_hip_shuffle.h (the verifiable shuffle: generators, mix, prover, verifier).
+EXPORTED_SHUFFLE = [
+    "eg_shuffle_generators", "eg_shuffle_generators_dev",
+    "eg_shuffle_mix", "eg_shuffle_mix_dev",
+    "eg_shuffle_prove", "eg_shuffle_prove_dev",
+    "eg_shuffle_verify", "eg_shuffle_verify_dev",
+]
+
 
 class NativeUnavailable(RuntimeError):
     pass
@@ -200,6 +208,10 @@ def _sig(lib: ctypes.CDLL) -> None:
         "eg_decrypt2_combine": ([P, P, P, S, S, P, P, P, P, P, P, P], I),
         "eg_decrypt2_check": ([P, S, S, P, P, P, P, P, P, P, P], I),
         "eg_decrypt2_verify": ([P, P, P, S, P, P, P, P], I),
+        "eg_shuffle_generators": ([P, P, P, S, P], I),
+        "eg_shuffle_mix": ([P, P, S, S, P, P, P, P], I),
+        "eg_shuffle_prove": ([P, P, P, P, S, S] + [P] * 12, I),
+        "eg_shuffle_verify": ([P, P, P, P, S, S] + [P] * 9 + [I, P, P], I),
     }
     sigs.update({name + dev: sig for name, sig in pairs.items() for dev in ("", "_dev")})
     for name, (args, res) in sigs.items():
