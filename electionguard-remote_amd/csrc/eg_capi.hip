@@ -538,44 +538,58 @@ static int pow_schedule_dev(eg_ctx* c, const PowShape& S, const FbTab& f0, const
   return EG_OK;
 }
 
-// Run a homogeneous batch of exponentiation jobs (device job records).
-// yout (comb jobs, optional): y_1..y_4 of every job, (kCombH-1) device elements per job, kept for a
-// later gather launch; ygat: the y_k array a gather launch (S.gather > 0) multiplies together.
-// tail, tail2 (optional): up to two more independent job populations (shapes tail->S, tail2->S)
-// appended to the LAST sub-launch so their short jobs fill that launch's tail (PowPart in
-// eg_kernels.hpp).
 // jobs per k_pow sub-launch (bounds the per-launch scratch: 32 or 64 comb entries per job)
 constexpr size_t kPowMaxJobs = (size_t)1 << 18;
 // jobs of a last sub-launch together with its tails that a caller may plan for (the verifier's
 // beta head in launch 1): bounds that launch's scratch to ~21 GB of 40-KB comb tables
 constexpr size_t kPowTailJobs = (size_t)1 << 19;
 
-struct PowTail {
-  PowShape S;
-  const uint32_t* jobs;
-  size_t njobs;
-  uint32_t* yout;
-  const uint32_t* ygat;
-  uint32_t* rout;  // residue pairs (tail->S.resid)
-  const uint32_t* ctab;  // shared comb table (tail->S.shared_comb)
+// One homogeneous population of exponentiation jobs (device job records) and the buffers its
+// shape needs.
+struct PowPop {
+  PowShape S{};
+  const uint32_t* jobs = nullptr;
+  size_t njobs = 0;
+  uint32_t* yout = nullptr;        // comb jobs, optional: y_1..y_4 of every job, (kCombH-1) device
+                                   // elements per job, kept for a later gather launch
+  const uint32_t* ygat = nullptr;  // the y_k array a gather population (S.gather > 0) multiplies together
+  uint32_t* rout = nullptr;        // residue pairs (S.resid), 2 device elements per job
+  const uint32_t* ctab = nullptr;  // shared comb table (S.shared_comb)
+  // jobs off .. off + cnt with their rows of the per-job buffers
+  PowPop part(size_t off, size_t cnt) const {
+    return PowPop{S, jobs + off * kJobWords, cnt, yout ? yout + off * (kCombH - 1) * kW : nullptr, ygat,
+                  rout ? rout + off * 2 * kW : nullptr, ctab};
+  }
 };
-static size_t pow_scratch_per_group(const PowShape& S) {
-  return (S.has_base && !S.shared_comb) ? (size_t)(S.comb ? (comb_blocks(S.blocks) << comb_rows(S.rows)) : 16u) * kW * 4 : 4;
-}
+// tail, tail2 (njobs == 0: none): up to two more independent populations appended to the LAST
+// sub-launch so their short jobs fill that launch's tail (PowPart in eg_kernels.hpp).
 // ct = true: the constant-time instantiation k_pow<F, true> for secret exponents (comb shapes
-// without fixed-base terms only); ctab: the shared comb table of S.shared_comb jobs.
+// without fixed-base terms only).
 // scratch (optional): the per-job table space of a batch of at most one workgroup and no tail
 // (the caller keeps the tables, e.g. g's shared comb table; it must hold kGroupsPerBlock jobs'
 // tables, since idle groups recompute the last job); default the W_SCR workspace.
-static int launch_pow(eg_ctx* c, const PowShape& S, const uint32_t* d_jobs, size_t njobs, const uint32_t* d_elems,
-                      const uint8_t* d_scal, uint32_t* d_out, FbTab f0, FbTab f1, uint32_t* yout = nullptr,
-                      const uint32_t* ygat = nullptr, const PowTail* tail = nullptr, uint32_t* rout = nullptr,
-                      bool ct = false, const uint32_t* ctab = nullptr, uint32_t* scratch = nullptr,
-                      const PowTail* tail2 = nullptr) {
-  if (tail && !tail->njobs) tail = nullptr;
-  if (tail2 && !tail2->njobs) tail2 = nullptr;
-  if (tail2 && !tail) std::swap(tail, tail2);
-  if (scratch && (tail || njobs > kPowMaxJobs || njobs > kGroupsPerBlock))
+struct PowOpts {
+  PowPop tail{}, tail2{};
+  bool ct = false;
+  uint32_t* scratch = nullptr;
+};
+// the options of a launch that only chooses the instantiation
+static PowOpts pow_ct(bool ct) {
+  PowOpts o;
+  o.ct = ct;
+  return o;
+}
+static size_t pow_scratch_per_group(const PowShape& S) {
+  return (S.has_base && !S.shared_comb) ? (size_t)(S.comb ? (comb_blocks(S.blocks) << comb_rows(S.rows)) : 16u) * kW * 4 : 4;
+}
+// Run the population `main`, in sub-launches of kPowMaxJobs jobs, with the options' tails.
+static int launch_pow(eg_ctx* c, const PowPop& main, const uint32_t* d_elems, const uint8_t* d_scal, uint32_t* d_out,
+                      FbTab f0, FbTab f1, const PowOpts& o = {}) {
+  const PowPop* pop[3] = {&main, nullptr, nullptr};
+  int np = 1;
+  for (const PowPop* t : {&o.tail, &o.tail2})
+    if (t->njobs) pop[np++] = t;
+  if (o.scratch && (np > 1 || main.njobs > kPowMaxJobs || main.njobs > kGroupsPerBlock))
     return fail(EG_ERR_ARG, "an explicit k_pow scratch takes one workgroup of jobs and no tail");
   // constant-time shapes: a comb or a 4-bit window (masked scans of their tables) without fixed-base
   // terms, or fixed-base terms alone from small-window tables (masked scans of 2^w-entry window columns)
@@ -584,66 +598,60 @@ static int launch_pow(eg_ctx* c, const PowShape& S, const uint32_t* d_jobs, size
     return f0.wbits <= kCtMaxWindow && f1.wbits <= kCtMaxWindow;
   };
   // every population of the launch: its shape and the buffers it needs
-  auto check = [&](const PowShape& X, const uint32_t* yg, const uint32_t* ro, const uint32_t* ct_tab) {
-    if (X.resid && (!X.comb || X.gather || !ro)) return fail(EG_ERR_ARG, "residue pairs need a plain comb shape and rout");
+  for (int i = 0; i < np; ++i) {
+    const PowShape& X = pop[i]->S;
+    if (X.resid && (!X.comb || X.gather || !pop[i]->rout))
+      return fail(EG_ERR_ARG, "residue pairs need a plain comb shape and rout");
     if (X.blocks > 1 && (X.blocks > 4 || !X.comb || X.gather || X.shared_comb))
       return fail(EG_ERR_ARG, "two to four column blocks need a plain comb shape");
-    if (X.shared_comb && (!X.comb || X.gather || X.resid || !ct_tab)) return fail(EG_ERR_ARG, "shared comb table missing");
+    if (X.shared_comb && (!X.comb || X.gather || X.resid || !pop[i]->ctab))
+      return fail(EG_ERR_ARG, "shared comb table missing");
     if (X.rows && (X.rows != 4 || !X.comb || X.gather || X.shared_comb))
       return fail(EG_ERR_ARG, "4-row combs are plain comb shapes");
-    if (ct && !ct_shape(X)) return fail(EG_ERR_ARG, "constant-time jobs are plain combs or small-window fixed-base terms");
-    if (X.gather && (!X.comb || !yg)) return fail(EG_ERR_ARG, "gather launch needs a comb shape and y_k source");
-    return (int)EG_OK;
-  };
-  int src = check(S, ygat, rout, ctab);
-  if (!src && tail) src = check(tail->S, tail->ygat, tail->rout, tail->ctab);
-  if (!src && tail2) src = check(tail2->S, tail2->ygat, tail2->rout, tail2->ctab);
-  if (src) return src;
-  if (!njobs && !tail) return EG_OK;
-  const size_t per = pow_scratch_per_group(S);
-  const size_t per1 = tail ? pow_scratch_per_group(tail->S) : 0;
-  const size_t per2 = tail2 ? pow_scratch_per_group(tail2->S) : 0;
-  // bound the per-launch scratch (table of 16/32 powers per job)
-  const size_t max_jobs = kPowMaxJobs;
-  MMCount mm_job, mm_tail, mm_tail2;
-  const uint32_t *sched = nullptr, *sched_tail = nullptr, *sched_tail2 = nullptr;
-  src = pow_schedule_dev(c, S, f0, f1, &sched, &mm_job);
-  if (!src && tail) src = pow_schedule_dev(c, tail->S, f0, f1, &sched_tail, &mm_tail);
-  if (!src && tail2) src = pow_schedule_dev(c, tail2->S, f0, f1, &sched_tail2, &mm_tail2);
-  if (src) return src;
+    if (o.ct && !ct_shape(X)) return fail(EG_ERR_ARG, "constant-time jobs are plain combs or small-window fixed-base terms");
+    if (X.gather && (!X.comb || !pop[i]->ygat)) return fail(EG_ERR_ARG, "gather launch needs a comb shape and y_k source");
+  }
+  if (!main.njobs && np == 1) return EG_OK;
+  size_t per[3] = {0, 0, 0};  // scratch bytes per group (table of 16/32 powers per job)
+  MMCount mm[3];
+  const uint32_t* sched[3] = {nullptr, nullptr, nullptr};
+  for (int i = 0; i < np; ++i) {
+    per[i] = pow_scratch_per_group(pop[i]->S);
+    const int rc = pow_schedule_dev(c, pop[i]->S, f0, f1, &sched[i], &mm[i]);
+    if (rc) return rc;
+  }
   size_t off = 0;
   do {
-    const size_t nj = std::min(max_jobs, njobs - off);
-    const bool last = off + nj >= njobs;
-    const size_t nt = (last && tail) ? tail->njobs : 0;
-    const size_t nt2 = (last && tail2) ? tail2->njobs : 0;
-    uint32_t* scr = scratch;
+    const size_t nj = std::min(kPowMaxJobs, main.njobs - off);
+    const int live = off + nj >= main.njobs ? np : 1;  // the tails ride in the last sub-launch
+    PowPop cur[3] = {main.part(off, nj)};
+    size_t need = padded_groups(nj) * per[0];
+    for (int i = 1; i < live; ++i) {
+      cur[i] = *pop[i];
+      need += padded_groups(cur[i].njobs) * per[i];
+    }
+    uint32_t* scr = o.scratch;
     if (!scr) {
-      const int rc = ws_get(c, W_SCR, padded_groups(nj) * per + padded_groups(nt) * per1 + padded_groups(nt2) * per2,
-                            (void**)&scr);
+      const int rc = ws_get(c, W_SCR, need, (void**)&scr);
       if (rc) return rc;
     }
-    PowPart P0{S, sched, d_jobs + off * kJobWords, (uint32_t)nj, grid_for(nj), scr,
-               yout ? yout + off * (kCombH - 1) * kW : nullptr, ygat, rout ? rout + off * 2 * kW : nullptr, ctab};
-    PowPart P1{}, P2{};
-    if (nt) {
-      P1 = PowPart{tail->S, sched_tail, tail->jobs, (uint32_t)nt, grid_for(nt),
-                   scr + padded_groups(nj) * per / 4, tail->yout, tail->ygat, tail->rout, tail->ctab};
+    PowPart P[3] = {};
+    size_t used = 0;
+    double mm_all = 0, mm_sqr = 0;
+    for (int i = 0; i < live; ++i) {
+      const PowPop& X = cur[i];
+      P[i] = PowPart{X.S, sched[i], X.jobs, (uint32_t)X.njobs, grid_for(X.njobs), scr + used / 4,
+                     X.yout, X.ygat, X.rout, X.ctab};
+      used += padded_groups(X.njobs) * per[i];
+      mm_all += (mm[i].mul + mm[i].sqr) * (double)X.njobs;
+      mm_sqr += mm[i].sqr * (double)X.njobs;
     }
-    if (nt2) {
-      P2 = PowPart{tail2->S, sched_tail2, tail2->jobs, (uint32_t)nt2, grid_for(nt2),
-                   scr + (padded_groups(nj) * per + padded_groups(nt) * per1) / 4, tail2->yout, tail2->ygat,
-                   tail2->rout, tail2->ctab};
-    }
-    const dim3 grid(P0.nblocks + P1.nblocks + P2.nblocks);
+    const dim3 grid(P[0].nblocks + P[1].nblocks + P[2].nblocks);
     ProfRec* pr = nullptr;
     uint64_t* clk = nullptr;
     if (c->timing) {
       // the record joins the window before anything can fail, so profile_end / destroy free its events
-      c->prof.push_back(ProfRec{nullptr, nullptr,
-                                (mm_job.mul + mm_job.sqr) * (double)nj + (mm_tail.mul + mm_tail.sqr) * (double)nt +
-                                    (mm_tail2.mul + mm_tail2.sqr) * (double)nt2,
-                                mm_job.sqr * (double)nj + mm_tail.sqr * (double)nt + mm_tail2.sqr * (double)nt2});
+      c->prof.push_back(ProfRec{nullptr, nullptr, mm_all, mm_sqr});
       pr = &c->prof.back();
       HIPCHK(hipEventCreate(&pr->a));
       HIPCHK(hipEventCreate(&pr->b));
@@ -654,16 +662,16 @@ static int launch_pow(eg_ctx* c, const PowShape& S, const uint32_t* d_jobs, size
       HIPCHK(hipEventRecord(pr->a, c->stream));
     }
     if (c->h.friendly) {
-      if (ct) hipLaunchKernelGGL((k_pow<true, true>), grid, dim3(kBlock), 0, c->stream, c->d, P0, P1, P2, d_elems, d_scal, d_out, f0, f1, clk);
-      else hipLaunchKernelGGL((k_pow<true, false>), grid, dim3(kBlock), 0, c->stream, c->d, P0, P1, P2, d_elems, d_scal, d_out, f0, f1, clk);
+      if (o.ct) hipLaunchKernelGGL((k_pow<true, true>), grid, dim3(kBlock), 0, c->stream, c->d, P[0], P[1], P[2], d_elems, d_scal, d_out, f0, f1, clk);
+      else hipLaunchKernelGGL((k_pow<true, false>), grid, dim3(kBlock), 0, c->stream, c->d, P[0], P[1], P[2], d_elems, d_scal, d_out, f0, f1, clk);
     } else {
-      if (ct) hipLaunchKernelGGL((k_pow<false, true>), grid, dim3(kBlock), 0, c->stream, c->d, P0, P1, P2, d_elems, d_scal, d_out, f0, f1, clk);
-      else hipLaunchKernelGGL((k_pow<false, false>), grid, dim3(kBlock), 0, c->stream, c->d, P0, P1, P2, d_elems, d_scal, d_out, f0, f1, clk);
+      if (o.ct) hipLaunchKernelGGL((k_pow<false, true>), grid, dim3(kBlock), 0, c->stream, c->d, P[0], P[1], P[2], d_elems, d_scal, d_out, f0, f1, clk);
+      else hipLaunchKernelGGL((k_pow<false, false>), grid, dim3(kBlock), 0, c->stream, c->d, P[0], P[1], P[2], d_elems, d_scal, d_out, f0, f1, clk);
     }
     HIPCHK(hipGetLastError());
     if (pr) HIPCHK(hipEventRecord(pr->b, c->stream));
     off += nj;
-  } while (off < njobs);
+  } while (off < main.njobs);
   return EG_OK;
 }
 
@@ -1047,34 +1055,26 @@ static int pow_host(eg_ctx* c, const uint8_t* base_be, const uint8_t* exp_be, ui
   int rc;
   const size_t nexp = exp_shared ? 1 : n;
   if ((rc = upload(c, W_EXP, exp_be, nexp * exp_bytes, (void**)&d_exp))) return rc;
-  PowShape S{};
-  S.nout = 1;
-  S.exp_bytes = exp_bytes;
-  std::vector<uint32_t> jobs(n * kJobWords, kNone);
+  const PowShape S = fbonly ? pow_fb_one() : pow_var(1, exp_bytes);  // fixed-base exponents are 32 bytes
+  auto jobs = new_jobs(n);
   for (size_t i = 0; i < n; ++i) {
-    uint32_t* J = &jobs[i * kJobWords];
-    J[0] = fbonly ? kNone : (uint32_t)i;
-    J[1] = exp_shared ? 0u : (uint32_t)i;
-    J[3] = (uint32_t)i;
-    J[5] = (uint32_t)i;
+    PowJob& J = jobs[i];
+    J.base = fbonly ? kNone : (uint32_t)i;
+    J.exp[0] = exp_shared ? 0u : (uint32_t)i;
+    J.out[0] = (uint32_t)i;
+    J.fb[0][0] = (uint32_t)i;
   }
-  if (fbonly) {
-    S.has_base = 0;
-    S.nfb[0] = 1;
-    S.tab[0][0] = 0;
-  } else {
-    S.has_base = 1;
+  if (!fbonly) {
     if ((rc = upload(c, W_IN0, base_be, n * 512, (void**)&d_base))) return rc;
     if ((rc = ws_get(c, W_E0, n * kW * 4, (void**)&d_e))) return rc;
     if ((rc = launch_import(c, d_base, n, d_e, nullptr))) return rc;
   }
-  if ((rc = upload(c, W_JOBS, jobs.data(), jobs.size() * 4, (void**)&d_jobs))) return rc;
+  if ((rc = upload(c, W_JOBS, jobs.data(), jobs.size() * sizeof(PowJob), (void**)&d_jobs))) return rc;
   if ((rc = ws_get(c, W_E1, n * kW * 4, (void**)&d_o))) return rc;
   FbTab f0 = fbonly ? *fbonly : c->gtab->tab();
   // eg_ctx_set_ct_pow: the window / fixed-base schedule of k_pow<F, true> (a public exponent, the
   // inverse's p - 2, keeps the variable-time instantiation)
-  const bool ct = c->ct_pow && exp_bytes == 32;
-  if ((rc = launch_pow(c, S, d_jobs, n, d_e, d_exp, d_o, f0, f0, nullptr, nullptr, nullptr, nullptr, ct))) return rc;
+  if ((rc = launch_pow(c, {S, d_jobs, n}, d_e, d_exp, d_o, f0, f0, pow_ct(c->ct_pow && exp_bytes == 32)))) return rc;
   if ((rc = ws_get(c, W_OUT, n * 512, (void**)&d_out))) return rc;
   if ((rc = launch_export(c, d_o, n, d_out))) return rc;
   HIPCHK(hipMemcpyAsync(out_be, d_out, n * 512, hipMemcpyDeviceToHost, c->stream));
@@ -1346,11 +1346,11 @@ static int identity_pow_jobs(eg_ctx* c, size_t n, bool fbonly, const uint32_t** 
     if (rc) return rc;
     auto jobs = new_jobs(n);
     for (size_t i = 0; i < n; ++i) {
-      uint32_t* J = &jobs[i * kJobWords];
-      J[0] = fbonly ? kNone : (uint32_t)i;
-      J[1] = (uint32_t)i;
-      J[3] = (uint32_t)i;
-      J[5] = (uint32_t)i;
+      PowJob& J = jobs[i];
+      J.base = fbonly ? kNone : (uint32_t)i;
+      J.exp[0] = (uint32_t)i;
+      J.out[0] = (uint32_t)i;
+      J.fb[0][0] = (uint32_t)i;
     }
     return cached_jobs(c, key, jobs, out);
   }
@@ -1365,20 +1365,13 @@ static int pow_dev(eg_ctx* c, const uint8_t* d_base_be, const uint8_t* d_exp_be,
   uint32_t *d_e = nullptr, *d_o = nullptr;
   int rc;
   if ((rc = identity_pow_jobs(c, n, fbonly != nullptr, &d_jobs))) return rc;
-  PowShape S{};
-  S.nout = 1;
-  S.exp_bytes = 32;
-  if (fbonly) {
-    S.nfb[0] = 1;
-    S.tab[0][0] = 0;
-  } else {
-    S.has_base = 1;
+  if (!fbonly) {
     if ((rc = ws_get(c, W_E0, n * kW * 4, (void**)&d_e))) return rc;
     if ((rc = launch_import(c, d_base_be, n, d_e, nullptr))) return rc;
   }
   if ((rc = ws_get(c, W_E1, n * kW * 4, (void**)&d_o))) return rc;
   FbTab f0 = fbonly ? *fbonly : c->gtab->tab();
-  if ((rc = launch_pow(c, S, d_jobs, n, d_e, d_exp_be, d_o, f0, f0, nullptr, nullptr, nullptr, nullptr, c->ct_pow != 0)))
+  if ((rc = launch_pow(c, {fbonly ? pow_fb_one() : pow_var(), d_jobs, n}, d_e, d_exp_be, d_o, f0, f0, pow_ct(c->ct_pow != 0))))
     return rc;
   return launch_export(c, d_o, n, d_out_be);
 }

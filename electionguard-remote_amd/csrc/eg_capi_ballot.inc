@@ -16,6 +16,17 @@
 // arithmetic addressing, the benchmark's kernels and plan) from a table-addressed one (the
 // entry points of eg_capi_manifest.inc: per-contest device tables).
 
+// The words of one cached host table: job records, or the u32 index tables that ride in the same
+// cached sets (built on a cache miss only).
+struct JobTable {
+  std::vector<uint32_t> w;
+  JobTable(std::vector<uint32_t> v) : w(std::move(v)) {}
+  JobTable(const std::vector<PowJob>& j) : w(j.size() * kJobWords) {
+    if (!w.empty()) std::memcpy(w.data(), j.data(), w.size() * 4);  // an empty table has no storage to copy
+  }
+};
+using JobSet = std::vector<JobTable>;
+
 // One device copy of a host job table (freed again when the upload fails).  EG_TEST_FAIL_JOBS=k
 // (read at context creation, tests only) makes the k-th upload of the context fail as an
 // out-of-memory hipMalloc would.
@@ -56,13 +67,17 @@ static int cached_jobs(eg_ctx* c, const std::string& key, const std::vector<uint
   *out = (const uint32_t*)it->second.ptr;
   return EG_OK;
 }
+// copies the table to words BEFORE the lookup: for callers that have already missed (identity_pow_jobs)
+static int cached_jobs(eg_ctx* c, const std::string& key, const std::vector<PowJob>& host, const uint32_t** out) {
+  return cached_jobs(c, key, JobTable(host).w, out);
+}
 
 // The job tables of one launch shape, cached as a set under key + "/" + name: a hit needs EVERY
 // name present, and a miss builds the host tables (make) and uploads all of them before any is
 // inserted, so an upload that fails (out of memory) leaves no partial set behind that a later
 // call could take for a hit and hand a null table to k_pow (ADVICE r03).
 static int cached_job_set(eg_ctx* c, const std::string& key, const std::vector<std::string>& names,
-                          const std::function<std::vector<std::vector<uint32_t>>()>& make,
+                          const std::function<JobSet()>& make,
                           std::vector<const uint32_t*>& out) {
   out.assign(names.size(), nullptr);
   bool hit = true;
@@ -82,11 +97,11 @@ static int cached_job_set(eg_ctx* c, const std::string& key, const std::vector<s
   }
   int rc = cache_bound(c);
   if (rc) return rc;
-  const std::vector<std::vector<uint32_t>> host = make();
+  const JobSet host = make();
   std::vector<DevBuf> bufs;
   for (const auto& h : host) {
     DevBuf b;
-    if ((rc = upload_job_table(c, h, &b))) {
+    if ((rc = upload_job_table(c, h.w, &b))) {
       for (auto& x : bufs) hipFree(x.ptr);
       return rc;
     }
@@ -99,16 +114,23 @@ static int cached_job_set(eg_ctx* c, const std::string& key, const std::vector<s
   return EG_OK;
 }
 
-static int upload_jobs(eg_ctx* c, Slot s, const std::vector<uint32_t>& host, const uint32_t** out) {
+static int upload_jobs(eg_ctx* c, Slot s, const std::vector<PowJob>& host, const uint32_t** out) {
   void* d = nullptr;
-  int rc = ws_get(c, s, std::max<size_t>(4, host.size() * 4), &d);
+  const size_t bytes = host.size() * sizeof(PowJob);
+  int rc = ws_get(c, s, std::max<size_t>(4, bytes), &d);
   if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(d, host.data(), host.size() * 4, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(d, host.data(), bytes, hipMemcpyHostToDevice, c->stream));
   *out = (const uint32_t*)d;
   return EG_OK;
 }
 
-static std::vector<uint32_t> new_jobs(size_t n) { return std::vector<uint32_t>(n * kJobWords, kNone); }
+// a host job table, uploaded into workspace slot s and run as one population of shape S
+static int launch_pow_jobs(eg_ctx* c, Slot s, const PowShape& S, const std::vector<PowJob>& J, const uint32_t* elems,
+                           const uint8_t* scal, uint32_t* out, FbTab f0, FbTab f1, const PowOpts& o = {}) {
+  const uint32_t* dj = nullptr;
+  const int rc = upload_jobs(c, s, J, &dj);
+  return rc ? rc : launch_pow(c, {S, dj, J.size()}, elems, scal, out, f0, f1, o);
+}
 
 static int launch_hash(eg_ctx* c, uint32_t n, std::vector<HashSrc> src, const uint8_t* proofs, uint32_t pw,
                        uint32_t ci0, uint32_t ci1, const uint8_t* pre_ok, const uint8_t* pre_ok2, uint32_t pre2_div,
@@ -281,16 +303,16 @@ static ManShape uniform_shape(size_t nc, size_t spc, size_t ph, uint32_t limit) 
 // device copy's address goes to.
 struct TableList {
   std::vector<std::string> names;
-  std::vector<std::function<std::vector<uint32_t>()>> make;
+  std::vector<std::function<JobTable()>> make;
   std::vector<const uint32_t**> dst;
-  void add(const std::string& name, const uint32_t** d, std::function<std::vector<uint32_t>()> f) {
+  void add(const std::string& name, const uint32_t** d, std::function<JobTable()> f) {
     names.push_back(name); dst.push_back(d); make.push_back(std::move(f));
   }
 };
 static int fetch_tables(eg_ctx* c, const std::string& key, const TableList& L) {
   std::vector<const uint32_t*> dev;
   const int rc = cached_job_set(c, key, L.names, [&]() {
-    std::vector<std::vector<uint32_t>> host;
+    JobSet host;
     for (const auto& f : L.make) host.push_back(f());
     return host;
   }, dev);
@@ -405,56 +427,45 @@ struct VerifyLayout {
       : ns(nbc * M.nsel), ncn(nbc * M.nc), off_c(ns * 4), off_neg(off_c + ncn * 2), off_negL(off_neg + ns) {}
 };
 // the alpha (beta == false) or beta jobs of ns selections
-static std::vector<uint32_t> verify_sel_jobs(const VerifyLayout& V, bool beta) {
+static std::vector<PowJob> verify_sel_jobs(const VerifyLayout& V, bool beta) {
   auto J = new_jobs(V.ns);
   for (size_t i = 0; i < V.ns; ++i) {
-    uint32_t* x = &J[i * kJobWords];
+    PowJob& x = J[i];
     const uint32_t c0 = (uint32_t)(i * 4), v0 = c0 + 1, c1 = c0 + 2, v1 = c0 + 3, e = beta ? 1u : 0u;
-    x[0] = (uint32_t)(i * 2) + e; x[1] = c0; x[2] = c1; x[3] = c0 + e; x[4] = c1 + e; x[5] = v0; x[7] = v1;
-    if (beta) x[8] = (uint32_t)(V.off_neg + i);
+    x.base = (uint32_t)(i * 2) + e; x.exp[0] = c0; x.exp[1] = c1; x.out[0] = c0 + e; x.out[1] = c1 + e;
+    x.fb[0][0] = v0; x.fb[1][0] = v1;
+    if (beta) x.fb[1][1] = (uint32_t)(V.off_neg + i);
   }
   return J;
 }
 // the contest a (b == false) or contest b jobs of class C, ballot-major: job bi * C.n + mi
-static std::vector<uint32_t> verify_contest_jobs(const ManShape& M, const ManShape::Class& C, const VerifyLayout& V,
+static std::vector<PowJob> verify_contest_jobs(const ManShape& M, const ManShape::Class& C, const VerifyLayout& V,
                                                  size_t nbc, bool b) {
   auto J = new_jobs(nbc * C.n);
   for (size_t bi = 0; bi < nbc; ++bi)
     for (size_t mi = 0; mi < C.n; ++mi) {
       const uint32_t k = M.member(C, mi), e = b ? 1u : 0u;
       const size_t j = bi * M.nc + k;  // the contest's place in every ballot-major array
-      uint32_t* x = &J[(bi * C.n + mi) * kJobWords];
+      PowJob& x = J[bi * C.n + mi];
       const uint32_t cc = (uint32_t)(V.off_c + j * 2);
-      x[0] = (uint32_t)(V.ns * 2 + j * 2) + e; x[1] = cc; x[3] = (uint32_t)(V.ns * 4 + j * 2) + e; x[5] = cc + 1;
-      if (b) x[6] = (uint32_t)(V.off_negL + j);
-      x[2] = (uint32_t)(bi * M.nsel + M.first_of(k));  // gather: the contest's first selection job (y_k source)
+      x.base = (uint32_t)(V.ns * 2 + j * 2) + e; x.exp[0] = cc; x.out[0] = (uint32_t)(V.ns * 4 + j * 2) + e;
+      x.fb[0][0] = cc + 1;
+      if (b) x.fb[0][1] = (uint32_t)(V.off_negL + j);
+      x.gather_src() = (uint32_t)(bi * M.nsel + M.first_of(k));  // the contest's first selection job (y_k source)
     }
   return J;
 }
 
-// One k_pow job population, and one launch_pow call of the contest populations: a main part and
-// up to two tails.
-struct Pop {
-  PowShape S;
-  const uint32_t* jobs;
-  size_t n;
-  const uint32_t* ygat;
-  Pop part(size_t off, size_t cnt) const { return Pop{S, jobs + off * kJobWords, cnt, ygat}; }
-  PowTail tail() const {
-    PowTail T{};
-    T.S = S; T.jobs = jobs; T.njobs = n; T.ygat = ygat;
-    return T;
-  }
-};
+// One launch_pow call of the contest populations: a main part and up to two tails.
 struct PowLaunch {
-  Pop main;
-  std::vector<Pop> tails;
+  PowPop main;
+  std::vector<PowPop> tails;
 };
 // The verifier's k_pow launches.  Launch 1 is alpha with the first xb beta jobs as its tail,
 // launch 2 the other betas with `l2` as tails, then `later`, one launch_pow call each.
 struct VerifyPlan {
   size_t xb = 0;
-  std::vector<Pop> l2;
+  std::vector<PowPop> l2;
   std::vector<PowLaunch> later;
 };
 
@@ -493,7 +504,7 @@ static size_t beta_head(size_t ns, size_t slots, size_t x0) {
 //     split into sub-launches, so only populations of at most kPowMaxJobs jobs ride as one.  At
 //     most 2 + (C - 2) + C <= 2 + 2 C launch_pow calls for C classes.  EG_CB_EARLY is ignored.
 static VerifyPlan plan_pow_launches(const eg_ctx* c, const ManShape& M, size_t ns, size_t ncn,
-                                    const std::vector<Pop>& pa, const std::vector<Pop>& pb) {
+                                    const std::vector<PowPop>& pa, const std::vector<PowPop>& pb) {
   VerifyPlan P;
   size_t slots = c->pow_slots;
   if (const char* ov = getenv("EG_POW_SLOTS")) slots = (size_t)strtoull(ov, nullptr, 10);  // test override
@@ -523,9 +534,9 @@ static VerifyPlan plan_pow_launches(const eg_ctx* c, const ManShape& M, size_t n
     return P;
   }
   P.xb = beta_head(ns, slots, 0);
-  std::vector<Pop> rest;
-  for (const Pop& p : pa) {
-    if (P.l2.size() < 2 && p.n <= kPowMaxJobs) P.l2.push_back(p);
+  std::vector<PowPop> rest;
+  for (const PowPop& p : pa) {
+    if (P.l2.size() < 2 && p.njobs <= kPowMaxJobs) P.l2.push_back(p);
     else rest.push_back(p);
   }
   if (debug)
@@ -534,7 +545,7 @@ static VerifyPlan plan_pow_launches(const eg_ctx* c, const ManShape& M, size_t n
   rest.insert(rest.end(), pb.begin(), pb.end());
   for (size_t i = 0; i < rest.size();) {
     PowLaunch L{rest[i++], {}};
-    while (L.tails.size() < 2 && i < rest.size() && rest[i].n <= kPowMaxJobs) L.tails.push_back(rest[i++]);
+    while (L.tails.size() < 2 && i < rest.size() && rest[i].njobs <= kPowMaxJobs) L.tails.push_back(rest[i++]);
     P.later.push_back(std::move(L));
   }
   return P;
@@ -613,45 +624,26 @@ static int verify_chunk_locked(eg_ctx* c, const ManShape& M, size_t nbc, const u
   // shader clock and a 0.6% higher clock (25% less comb-table traffic) in a same-box A/B
   // (profiles/r03r_ab_sel43.log)
   const uint32_t srows = c->sel_rows, sblocks = c->sel_blocks;
-  PowShape SA{};  // alpha: a0 = alpha^c0 g^v0, a1 = alpha^c1 g^v1  (comb shared by c0, c1)
-  SA.has_base = 1; SA.nout = 2; SA.nfb[0] = 1; SA.nfb[1] = 1; SA.exp_bytes = 32; SA.comb = 1; SA.resid = 1;
-  SA.rows = srows; SA.blocks = sblocks; SA.tab[0][0] = 0; SA.tab[1][0] = 0;
-  PowShape SB{};  // beta: b0 = beta^c0 K^v0, b1 = beta^c1 K^v1 g^-c1  (comb shared by c0, c1)
-  SB.has_base = 1; SB.nout = 2; SB.nfb[0] = 1; SB.nfb[1] = 2; SB.exp_bytes = 32; SB.comb = 1; SB.resid = 1;
-  SB.rows = srows; SB.blocks = sblocks; SB.tab[0][0] = 1; SB.tab[1][0] = 1; SB.tab[1][1] = 0;
-  std::vector<Pop> pa, pb;
+  // alpha: a0 = alpha^c0 g^v0, a1 = alpha^c1 g^v1; beta: b0 = beta^c0 K^v0, b1 = beta^c1 K^v1 g^-c1
+  // (one comb shared by c0, c1 each)
+  const PowPop PA{pow_sel_pair(false, srows, sblocks), jA, ns, YA, nullptr, RZ};
+  const PowPop PB{pow_sel_pair(true, srows, sblocks), jB, ns, YB, nullptr, RZ + ns * 2 * kW};
+  std::vector<PowPop> pa, pb;
   for (size_t ci = 0; ci < ncls; ++ci) {
     const uint32_t gather = gat ? M.cls[ci].spc : 0u;
     const size_t n = nbc * M.cls[ci].n;
-    PowShape SCA{};  // contest a = A^c g^v
-    SCA.has_base = 1; SCA.nout = 1; SCA.nfb[0] = 1; SCA.exp_bytes = 32; SCA.tab[0][0] = 0;
-    SCA.comb = gat ? 1u : 0u; SCA.gather = gather;
-    PowShape SCB{};  // contest b = B^c K^v g^-Lc
-    SCB.has_base = 1; SCB.nout = 1; SCB.nfb[0] = 2; SCB.exp_bytes = 32; SCB.tab[0][0] = 1; SCB.tab[0][1] = 0;
-    SCB.comb = gat ? 1u : 0u; SCB.gather = gather;
-    pa.push_back(Pop{SCA, jCA[ci], n, YA});
-    pb.push_back(Pop{SCB, jCB[ci], n, YB});
+    // contest a = A^c g^v, contest b = B^c K^v g^-Lc
+    pa.push_back(PowPop{pow_sel_gather(false, gather), jCA[ci], n, nullptr, YA});
+    pb.push_back(PowPop{pow_sel_gather(true, gather), jCB[ci], n, nullptr, YB});
   }
   const VerifyPlan P = plan_pow_launches(c, M, ns, ncn, pa, pb);
   const size_t xb = P.xb;
-  auto launch = [&](const PowShape& S, const uint32_t* jobs, size_t n, uint32_t* yout, const uint32_t* ygat,
-                    uint32_t* rout, const std::vector<PowTail>& tl) {
-    return launch_pow(c, S, jobs, n, E, SC, COMM, G, K, yout, ygat, tl.size() > 0 ? &tl[0] : nullptr, rout, false,
-                      nullptr, nullptr, tl.size() > 1 ? &tl[1] : nullptr);
+  auto launch = [&](const PowPop& main, const std::vector<PowPop>& tl) {
+    return launch_pow(c, main, E, SC, COMM, G, K, {tl.size() > 0 ? tl[0] : PowPop{}, tl.size() > 1 ? tl[1] : PowPop{}});
   };
-  auto tails_of = [](const std::vector<Pop>& pops) {
-    std::vector<PowTail> tl;
-    for (const Pop& p : pops) tl.push_back(p.tail());
-    return tl;
-  };
-  {
-    PowTail H{};  // the first xb beta jobs fill launch 1's last round
-    H.S = SB; H.jobs = jB; H.njobs = xb; H.yout = YB; H.rout = RZ + ns * 2 * kW;
-    if ((rc = launch(SA, jA, ns, YA, nullptr, RZ, {H}))) return rc;
-  }
-  if ((rc = launch(SB, jB + xb * kJobWords, ns - xb, gat ? YB + xb * (kCombH - 1) * kW : nullptr, nullptr,
-                   RZ + (ns + xb) * 2 * kW, tails_of(P.l2))))
-    return rc;
+  // the first xb beta jobs fill launch 1's last round
+  if ((rc = launch(PA, {PB.part(0, xb)}))) return rc;
+  if ((rc = launch(PB.part(xb, ns - xb), P.l2))) return rc;
   // alpha^q == 1 and beta^q == 1 (valid residues) fold into the range flags the hash check reads
   LAUNCH_F(c, k_resid_check, dim3(grid_for(ns)), c->d, RZ, (uint32_t)ns, LTP, 2u);
   LAUNCH_F(c, k_resid_check, dim3(grid_for(ns)), c->d, RZ + ns * 2 * kW, (uint32_t)ns, LTP + 1, 2u);
@@ -664,7 +656,7 @@ static int verify_chunk_locked(eg_ctx* c, const ManShape& M, size_t nbc, const u
   contest_flags(c, M, T, LTP, ncn, CRF);
   HIPCHK(hipGetLastError());
   for (const PowLaunch& l : P.later)
-    if ((rc = launch(l.main.S, l.main.jobs, l.main.n, nullptr, l.main.ygat, nullptr, tails_of(l.tails)))) return rc;
+    if ((rc = launch(l.main, l.tails))) return rc;
   // 5. canonical bytes of commitments and contest aggregates
   if ((rc = launch_export(c, COMM, ns * 4 + ncn * 2, COMM_BE))) return rc;
   if ((rc = launch_export(c, CP, ncn * 2, CP_BE))) return rc;
@@ -886,30 +878,30 @@ struct EncryptLayout {
 //   1  alpha = g^R ; a_real = g^u                -> slot 0
 //   2  beta = K^R g^m ; b_real = K^u             -> slot 1
 //   3  a_fake = g^sf ; b_fake = K^sf g^sg       -> slots 2, 3
-static std::vector<uint32_t> encrypt_sel_jobs(const EncryptLayout& V, int which) {
+static std::vector<PowJob> encrypt_sel_jobs(const EncryptLayout& V, int which) {
   auto J = new_jobs(V.ns);
   for (size_t i = 0; i < V.ns; ++i) {
     const uint32_t R = (uint32_t)(i * 4), u = R + 1;
     const uint32_t dm = (uint32_t)(V.off_der + i * 3), sf = dm + 1, sg = dm + 2;
     const uint32_t cm = (uint32_t)(V.oCM + i * 4);
-    uint32_t* x = &J[i * kJobWords];
+    PowJob& x = J[i];
     if (which == 1) {
-      x[3] = (uint32_t)(V.oCT + i * 2); x[4] = cm; x[5] = R; x[7] = u;
+      x.out[0] = (uint32_t)(V.oCT + i * 2); x.out[1] = cm; x.fb[0][0] = R; x.fb[1][0] = u;
     } else if (which == 2) {
-      x[3] = (uint32_t)(V.oCT + i * 2 + 1); x[4] = cm + 1; x[5] = R; x[6] = dm; x[7] = u;
+      x.out[0] = (uint32_t)(V.oCT + i * 2 + 1); x.out[1] = cm + 1; x.fb[0][0] = R; x.fb[0][1] = dm; x.fb[1][0] = u;
     } else {
-      x[3] = cm + 2; x[4] = cm + 3; x[5] = sf; x[7] = sf; x[8] = sg;
+      x.out[0] = cm + 2; x.out[1] = cm + 3; x.fb[0][0] = sf; x.fb[1][0] = sf; x.fb[1][1] = sg;
     }
   }
   return J;
 }
 // the contest commitments a = g^u_c ; b = K^u_c (they do not depend on the contests' sizes)
-static std::vector<uint32_t> encrypt_contest_jobs(const EncryptLayout& V) {
+static std::vector<PowJob> encrypt_contest_jobs(const EncryptLayout& V) {
   auto J = new_jobs(V.ncn);
   for (size_t j = 0; j < V.ncn; ++j) {
-    uint32_t* a = &J[j * kJobWords];
-    a[3] = (uint32_t)(V.oCC + j * 2); a[4] = (uint32_t)(V.oCC + j * 2 + 1);
-    a[5] = (uint32_t)(V.off_cn + j); a[7] = (uint32_t)(V.off_cn + j);
+    PowJob& a = J[j];
+    a.out[0] = (uint32_t)(V.oCC + j * 2); a.out[1] = (uint32_t)(V.oCC + j * 2 + 1);
+    a.fb[0][0] = (uint32_t)(V.off_cn + j); a.fb[1][0] = (uint32_t)(V.off_cn + j);
   }
   return J;
 }
@@ -962,21 +954,14 @@ static int encrypt_chunk_locked(eg_ctx* c, const ManShape& M, size_t nb, const u
   // last round; the contest aggregates (products of j1/j2's ciphertexts) follow.  g^m (m the
   // vote, 0 or 1) takes radix window 0 only: one multiply instead of a full fixed-base term.
   {
-    PowShape S{};
-    S.nout = 2; S.nfb[0] = 1; S.nfb[1] = 1; S.exp_bytes = 32;
-    PowTail TL{};
-    TL.S.nout = 2; TL.S.nfb[0] = 1; TL.S.nfb[1] = 1; TL.S.exp_bytes = 32; TL.S.tab[1][0] = 1;
-    TL.jobs = j4; TL.njobs = ncn;
-    if ((rc = launch_pow(c, S, j1, ns, U, SC, U, G, K, nullptr, nullptr, &TL, nullptr, ct))) return rc;
+    PowShape S = pow_fb_pair(false);
+    S.tab[1][0] = 0;  // g^R ; g^u: both from g's table
+    if ((rc = launch_pow(c, {S, j1, ns}, U, SC, U, G, K, {{pow_fb_pair(false), j4, ncn}, {}, ct}))) return rc;
   }
   {
-    PowShape S{};
-    S.nout = 2; S.nfb[0] = 2; S.nfb[1] = 1; S.exp_bytes = 32; S.tab[0][0] = 1; S.tab[0][1] = 0; S.tab[1][0] = 1;
-    S.fb_small[0][1] = 1;
-    PowTail TL{};
-    TL.S.nout = 2; TL.S.nfb[0] = 1; TL.S.nfb[1] = 2; TL.S.exp_bytes = 32; TL.S.tab[1][0] = 1; TL.S.tab[1][1] = 0;
-    TL.jobs = j3; TL.njobs = ns;
-    if ((rc = launch_pow(c, S, j2, ns, U, SC, U, G, K, nullptr, nullptr, &TL, nullptr, ct))) return rc;
+    PowShape S = pow_fb_pair(false);  // K^R g^m ; K^u
+    S.nfb[0] = 2; S.tab[0][0] = 1; S.fb_small[0][1] = 1;
+    if ((rc = launch_pow(c, {S, j2, ns}, U, SC, U, G, K, {{pow_fb_pair(true), j3, ns}, {}, ct}))) return rc;
   }
   hipLaunchKernelGGL(k_enc_order, dim3(cgrid(ns * (2 * kW / 4))), dim3(256), 0, c->stream, U + oCM * kW, d_votes,
                      (uint32_t)ns);
@@ -1137,16 +1122,15 @@ static int g_comb_table(eg_ctx* c, const uint32_t** out) {
       // a workgroup's idle groups recompute job 0 into their own table slots: room for all of them
       HIPCHK(hipMalloc(&tab, (size_t)kGroupsPerBlock * (1 << kCombH) * kW * 4));
       auto J = new_jobs(1);
-      J[0] = 0;
-      const uint32_t* dj = nullptr;
-      PowShape S{};
-      S.has_base = 1; S.nout = 0; S.exp_bytes = 32; S.comb = 1;
+      J[0].base = 0;
+      // no output: only the comb's precompute runs
+      PowShape S = pow_var(0);
+      S.comb = 1;
       const FbTab G = c->gtab->tab();
       // the job's subset table is written straight into `tab` (its scratch, job 0 of the launch)
-      if ((rc = upload_jobs(c, W_JOBS, J, &dj)) ||
-          (rc = launch_pow(c, S, dj, 1, d_g, nullptr, nullptr, G, G, nullptr, nullptr, nullptr, nullptr, false,
-                           nullptr, tab)))
-        return rc;
+      PowOpts o;
+      o.scratch = tab;
+      if ((rc = launch_pow_jobs(c, W_JOBS, S, J, d_g, nullptr, nullptr, G, G, o))) return rc;
       HIPCHK(hipStreamSynchronize(c->stream));
       return EG_OK;
     };
@@ -1160,6 +1144,33 @@ static int g_comb_table(eg_ctx* c, const uint32_t** out) {
   }
   *out = c->d_gcomb;
   return EG_OK;
+}
+
+// The trustee's launch, under k_pow<F, true> (fixed schedule, every table read a masked scan of
+// the column block's whole table: 16 entries for the pair's 4-row comb, 32 for g's shared table),
+// the only place the secret share and the proof nonces go.  E: the imported pads, pad i at element
+// i * pad_stride; SC: the scalars [secret][nonce x n]; gc: g's shared comb table.  O, 3 per item:
+//   O[3 i] = pad^secret, O[3 i + 2] = pad^nonce   one comb per pad, shared by both exponents
+//   O[3 i + 1] = g^nonce                          from gc: the short jobs fill the pair launch's tail
+static int trustee_pair_launch(eg_ctx* c, const uint32_t* gc, const uint32_t* E, size_t pad_stride, const uint8_t* SC,
+                               size_t n, uint32_t* O) {
+  int rc;
+  auto JA = new_jobs(n), JB = new_jobs(n);
+  for (size_t i = 0; i < n; ++i) {
+    PowJob& a = JA[i];
+    a.base = (uint32_t)(i * pad_stride); a.exp[0] = 0; a.exp[1] = (uint32_t)(1 + i);
+    a.out[0] = (uint32_t)(i * 3); a.out[1] = (uint32_t)(i * 3 + 2);
+    PowJob& b = JB[i];
+    b.base = 0; b.exp[0] = (uint32_t)(1 + i); b.out[0] = (uint32_t)(i * 3 + 1);
+  }
+  const uint32_t *ja, *jb;
+  if ((rc = upload_jobs(c, W_JOBS, JA, &ja)) || (rc = upload_jobs(c, W_H1, JB, &jb))) return rc;
+  const FbTab G = c->gtab->tab();
+  PowOpts o;
+  o.tail = PowPop{pow_shared_comb(), jb, n};
+  o.tail.ctab = gc;
+  o.ct = true;
+  return launch_pow(c, {pow_ct_pair(c->ct_rows), ja, n}, E, SC, O, G, G, o);
 }
 
 extern "C" int eg_trustee_decrypt_batch(eg_ctx* c, const uint8_t secret_be[32], const uint8_t qbar_be[32],
@@ -1183,15 +1194,13 @@ extern "C" int eg_trustee_decrypt_batch(eg_ctx* c, const uint8_t secret_be[32], 
     uint8_t* d_s = nullptr;
     uint32_t* d_o = nullptr;
     auto JK = new_jobs(1);
-    JK[1] = 0;  // exponent: the secret (row 0 of d_s)
-    JK[3] = 0;  // output element 0
-    const uint32_t* jk = nullptr;
-    PowShape S{};
-    S.has_base = 1; S.nout = 1; S.exp_bytes = 32; S.comb = 1; S.shared_comb = 1;
+    JK[0].exp[0] = 0;  // the secret (row 0 of d_s)
+    JK[0].out[0] = 0;
+    PowPop PK{pow_shared_comb(), nullptr, 1};
+    PK.ctab = gc;
     const FbTab G0 = c->gtab->tab();
     if ((rc = upload(c, W_SCAL, secret_be, 32, (void**)&d_s)) || (rc = ws_get(c, W_E1, kW * 4, (void**)&d_o)) ||
-        (rc = upload_jobs(c, W_JOBS, JK, &jk)) ||
-        (rc = launch_pow(c, S, jk, 1, nullptr, d_s, d_o, G0, G0, nullptr, nullptr, nullptr, nullptr, true, gc)) ||
+        (rc = upload_jobs(c, W_JOBS, JK, &PK.jobs)) || (rc = launch_pow(c, PK, nullptr, d_s, d_o, G0, G0, pow_ct(true))) ||
         (rc = ws_get(c, W_KBE, 512, (void**)&d_Ki)) || (rc = launch_export(c, d_o, 1, d_Ki)))
       return rc;
     HIPCHK(hipStreamSynchronize(c->stream));  // the batch below may grow (reallocate) the slots it used
@@ -1206,27 +1215,8 @@ extern "C" int eg_trustee_decrypt_batch(eg_ctx* c, const uint8_t secret_be[32], 
   if ((rc = ws_get(c, W_E0, n * 2 * kW * 4, (void**)&E))) return rc;
   if ((rc = launch_import(c, d_t, n * 2, E, nullptr))) return rc;
   if ((rc = ws_get(c, W_E1, n * 3 * kW * 4, (void**)&O))) return rc;
-  auto JA = new_jobs(n), JB = new_jobs(n);
-  for (size_t i = 0; i < n; ++i) {
-    uint32_t* a = &JA[i * kJobWords];
-    a[0] = (uint32_t)(i * 2); a[1] = 0; a[2] = (uint32_t)(1 + i); a[3] = (uint32_t)(i * 3); a[4] = (uint32_t)(i * 3 + 2);
-    uint32_t* b = &JB[i * kJobWords];
-    b[0] = 0; b[1] = (uint32_t)(1 + i); b[3] = (uint32_t)(i * 3 + 1);
-  }
-  const uint32_t *ja, *jb;
-  if ((rc = upload_jobs(c, W_JOBS, JA, &ja)) || (rc = upload_jobs(c, W_H1, JB, &jb))) return rc;
-  const FbTab G = c->gtab->tab();
-  // The secret share s (or P_l(x_i)) and the proof nonces u only ever drive the constant-time
-  // comb (k_pow<F, true>): fixed schedule, every table read a masked scan of the column
-  // block's whole table (16 entries for the pair's 4-row comb, 32 for g's shared table).
-  {
-    PowShape S{};  // M = pad^s, b = pad^u  (comb shared by s, u: 4 rows x 2 blocks, 16-entry scans)
-    S.has_base = 1; S.nout = 2; S.exp_bytes = 32; S.comb = 1; S.rows = c->ct_rows; S.blocks = c->ct_rows == 4 ? 2u : 0u;
-    PowTail T{};  // a = g^u from g's shared comb table: the short jobs fill the pair launch's tail
-    T.S.has_base = 1; T.S.nout = 1; T.S.exp_bytes = 32; T.S.comb = 1; T.S.shared_comb = 1;
-    T.jobs = jb; T.njobs = n; T.ctab = gc;
-    if ((rc = launch_pow(c, S, ja, n, E, SC, O, G, G, nullptr, nullptr, &T, nullptr, true))) return rc;
-  }
+  // M = pad^s, a = g^u, b = pad^u of the share s (or P_l(x_i)) and the proof nonces u
+  if ((rc = trustee_pair_launch(c, gc, E, 2, SC, n, O))) return rc;
   if ((rc = ws_get(c, W_BE0, n * 3 * 512, (void**)&OBE))) return rc;
   if ((rc = launch_export(c, O, n * 3, OBE))) return rc;
   if ((rc = ws_get(c, W_OK0, n * 32, (void**)&CH))) return rc;
@@ -1273,6 +1263,59 @@ static int share_key_table(eg_ctx* c, const uint8_t K_be[512], eg_fixed_base** o
   return EG_OK;
 }
 
+// The commitments a Chaum-Pedersen proof (c, v) of M = A^x under X = g^x answers for:
+//   a = g^v X^c,  b = A^v M^c
+// for n items j = t k + i (text t, key i; k = 1: one key per item or one for all), recomputed
+// from imported elements E and 32-byte scalars SC into O and exported to OBE.
+struct CpLayout {
+  size_t n, k;
+  uint32_t eX, nX;    // X_j = element eX + j % nX (unused with tables)
+  uint32_t eA, eM;    // text t's (A, B) = elements eA + 2 t, + 1;  M_j = element eM + j
+  uint32_t sC, sV, ds;  // c_j = scalar sC + ds j, v_j = scalar sV + ds j
+  uint32_t sNeg;      // kNone, or -c_j = scalar sNeg + j, which then stands in c_j's place
+  uint32_t so;        // a_j -> output so j, b_j -> so j + 1; the first so n outputs are exported
+  uint32_t oT, dT;    // the factors A^v, M^c of b_j -> outputs oT + dT j, + 1
+  // none: X_j is a variable base.  Else k radix tables, key i's X from tabs[i] next to g's: the
+  // jobs of a are key-major and every table takes one launch (k = 1: one table, one launch)
+  std::vector<FbTab> tabs;
+};
+static int cp_recompute(eg_ctx* c, const CpLayout& L, const uint32_t* E, const uint8_t* SC, uint32_t* O, uint8_t* OBE) {
+  int rc;
+  const size_t n = L.n, k = L.k, m = n / k;
+  const bool tabs = !L.tabs.empty();
+  if (tabs ? L.tabs.size() != k : !L.nX) return fail(EG_ERR_ARG, "Chaum-Pedersen layout: k tables, or nX variable bases");
+  auto JA = new_jobs(n), JB = new_jobs(n), JC = new_jobs(n);
+  for (size_t j = 0; j < n; ++j) {
+    const size_t t = j / k, i = j % k;
+    const uint32_t vv = L.sV + L.ds * (uint32_t)j, cc = L.sNeg != kNone ? L.sNeg + (uint32_t)j : L.sC + L.ds * (uint32_t)j;
+    PowJob& a = JA[tabs ? i * m + t : j];  // a = X^c g^v
+    a.out[0] = L.so * (uint32_t)j; a.fb[0][0] = vv;
+    if (tabs) a.fb[0][1] = cc;
+    else a.base = L.eX + (uint32_t)(j % L.nX), a.exp[0] = cc;
+    PowJob& b = JB[j];  // A^v
+    b.base = L.eA + 2 * (uint32_t)t; b.exp[0] = vv; b.out[0] = L.oT + L.dT * (uint32_t)j;
+    PowJob& d = JC[j];  // M^c
+    d.base = L.eM + (uint32_t)j; d.exp[0] = cc; d.out[0] = L.oT + L.dT * (uint32_t)j + 1;
+  }
+  const uint32_t *ja, *jb, *jc;
+  if ((rc = upload_jobs(c, W_JOBS, JA, &ja)) || (rc = upload_jobs(c, W_H1, JB, &jb)) ||
+      (rc = upload_jobs(c, W_H2, JC, &jc)))
+    return rc;
+  const FbTab G = c->gtab->tab();
+  if (tabs) {  // g^v (fb0) * X^c (fb1)
+    const PowPop A{pow_two_table(), ja, n};
+    for (size_t i = 0; i < k; ++i)
+      if ((rc = launch_pow(c, A.part(i * m, m), E, SC, O, G, L.tabs[i]))) return rc;
+  } else if ((rc = launch_pow(c, {pow_var(1, 32, 1), ja, n}, E, SC, O, G, G))) {
+    return rc;
+  }
+  if ((rc = launch_pow(c, {pow_var(), jb, n}, E, SC, O, G, G))) return rc;
+  if ((rc = launch_pow(c, {pow_var(), jc, n}, E, SC, O, G, G))) return rc;
+  LAUNCH_F(c, k_mul, dim3(grid_for(n)), c->d, O + L.oT * kW, L.dT, O + (L.oT + 1) * kW, L.dT, (uint32_t)n, O + kW, L.so);
+  HIPCHK(hipGetLastError());
+  return launch_export(c, O, n * L.so, OBE);
+}
+
 extern "C" int eg_verify_shares(eg_ctx* c, const uint8_t qbar_be[32], const uint8_t* Ki_be, const uint8_t* texts,
                                 const uint8_t* M_be, const uint8_t* proof, size_t n, uint8_t* ok) {
   if (!c || !qbar_be || (n && (!Ki_be || !texts || !M_be || !proof || !ok))) return fail(EG_ERR_ARG, "null argument");
@@ -1306,42 +1349,16 @@ extern "C" int eg_verify_shares(eg_ctx* c, const uint8_t qbar_be[32], const uint
     for (size_t i = 1; i < n && same; ++i) same = std::memcmp(Ki_be, Ki_be + i * 512, 512) == 0;
     if (same && (rc = share_key_table(c, Ki_be, &kt))) return rc;
   }
-  auto JA = new_jobs(n), JB = new_jobs(n), JC = new_jobs(n);
-  for (size_t i = 0; i < n; ++i) {
-    const uint32_t vv = (uint32_t)(i * 2 + 1), cc = c->resp_plus ? (uint32_t)(2 * n + i) : (uint32_t)(i * 2);
-    uint32_t* a = &JA[i * kJobWords];  // a = Ki^c g^v
-    if (kt) {
-      a[3] = (uint32_t)(i * 4); a[5] = vv; a[6] = cc;
-    } else {
-      a[0] = (uint32_t)i; a[1] = cc; a[3] = (uint32_t)(i * 4); a[5] = vv;
-    }
-    uint32_t* b = &JB[i * kJobWords];  // pad^v
-    b[0] = (uint32_t)(n + i * 2); b[1] = vv; b[3] = (uint32_t)(i * 4 + 2);
-    uint32_t* d = &JC[i * kJobWords];  // M^c
-    d[0] = (uint32_t)(3 * n + i); d[1] = cc; d[3] = (uint32_t)(i * 4 + 3);
-  }
-  const uint32_t *ja, *jb, *jc;
-  if ((rc = upload_jobs(c, W_JOBS, JA, &ja)) || (rc = upload_jobs(c, W_H1, JB, &jb)) ||
-      (rc = upload_jobs(c, W_H2, JC, &jc)))
-    return rc;
-  const FbTab G = c->gtab->tab();
-  PowShape S1{};
-  if (kt) {  // g^v (fb0) * K_i^c (fb1)
-    S1.nout = 1; S1.nfb[0] = 2; S1.exp_bytes = 32; S1.tab[0][0] = 0; S1.tab[0][1] = 1;
-    if ((rc = launch_pow(c, S1, ja, n, E, SC, O, G, kt->tab()))) return rc;
-  } else {
-    S1.has_base = 1; S1.nout = 1; S1.nfb[0] = 1; S1.exp_bytes = 32;
-    if ((rc = launch_pow(c, S1, ja, n, E, SC, O, G, G))) return rc;
-  }
-  PowShape S2{};
-  S2.has_base = 1; S2.nout = 1; S2.exp_bytes = 32;
-  if ((rc = launch_pow(c, S2, jb, n, E, SC, O, G, G))) return rc;
-  if ((rc = launch_pow(c, S2, jc, n, E, SC, O, G, G))) return rc;
-  LAUNCH_F(c, k_mul, dim3(grid_for(n)), c->d, O + 2 * kW, 4u, O + 3 * kW, 4u,
-                     (uint32_t)n, O + kW, 4u);
-  HIPCHK(hipGetLastError());
   if ((rc = ws_get(c, W_BE0, n * 4 * 512, (void**)&OBE))) return rc;
-  if ((rc = launch_export(c, O, n * 4, OBE))) return rc;
+  // elements [K_i (n)][pad, data (2 n)][M (n)], scalars [c, v (2 n)][-c (n): the plus convention
+  // raises K_i and M to -c]; rows of four outputs (a, b, pad^v, M^c)
+  CpLayout CP{};
+  CP.n = n; CP.k = 1;
+  CP.eX = 0; CP.nX = (uint32_t)n; CP.eA = (uint32_t)n; CP.eM = (uint32_t)(3 * n);
+  CP.sC = 0; CP.sV = 1; CP.ds = 2; CP.sNeg = c->resp_plus ? (uint32_t)(2 * n) : kNone;
+  CP.so = 4; CP.oT = 2; CP.dT = 4;
+  if (kt) CP.tabs = {kt->tab()};
+  if ((rc = cp_recompute(c, CP, E, SC, O, OBE))) return rc;
   if ((rc = ws_get(c, W_OK1, n, (void**)&d_ok))) return rc;
   const uint8_t* pads = IN + n * 512;
   if ((rc = launch_hash(c, (uint32_t)n,

@@ -357,10 +357,11 @@ static int b2_encrypt_chunk_locked(eg_ctx* c, const B2Shape& M, size_t nbc, cons
     return cached_job_set(c, key, {"T", "CT"}, [&]() {
       auto J = new_jobs(ns);
       for (size_t i = 0; i < ns; ++i) {  // alpha = g^R ; beta = K^R g^m
-        uint32_t* x = &J[i * kJobWords];
-        x[3] = (uint32_t)(i * 2); x[4] = x[3] + 1; x[5] = x[3]; x[7] = x[3]; x[8] = x[3] + 1;
+        PowJob& x = J[i];
+        x.out[0] = (uint32_t)(i * 2); x.out[1] = x.out[0] + 1;
+        x.fb[0][0] = x.out[0]; x.fb[1][0] = x.out[0]; x.fb[1][1] = x.out[0] + 1;
       }
-      return std::vector<std::vector<uint32_t>>{M.table, std::move(J)};
+      return JobSet{M.table, std::move(J)};
     }, tv);
   };
   if ((rc = tables())) return rc;
@@ -373,12 +374,7 @@ static int b2_encrypt_chunk_locked(eg_ctx* c, const B2Shape& M, size_t nbc, cons
                      (uint64_t)M.SN, (uint64_t)ncn, RSUM, SUMV);
   HIPCHK(hipGetLastError());
   // 2. ciphertexts, their bytes straight into the caller's rows, and the aggregates
-  {
-    PowShape S{};
-    S.nout = 2; S.nfb[0] = 1; S.nfb[1] = 2; S.exp_bytes = 32; S.tab[1][0] = 1; S.tab[1][1] = 0;
-    if ((rc = launch_pow(c, S, tv[1], ns, E, SC, E, G, K, nullptr, nullptr, nullptr, nullptr, c->ct_encrypt != 0)))
-      return rc;
-  }
+  if ((rc = launch_pow(c, {pow_fb_pair(true), tv[1], ns}, E, SC, E, G, K, pow_ct(c->ct_encrypt != 0)))) return rc;
   if ((rc = launch_export(c, E, ns * 2, cts))) return rc;
   if ((rc = b2_aggregates(c, M, T, nbc, E, AGG, AGG_BE))) return rc;
   // 3. every class's items, gathered

@@ -110,10 +110,7 @@ static int pow_latency(eg_ctx* c, const uint8_t* base_be, const uint8_t* exp_be,
     HIPCHK(hipStreamSynchronize(c->stream));
     return EG_OK;
   }
-  PowShape S{};
-  S.has_base = 1;
-  S.nout = 1;
-  S.exp_bytes = 32;
+  const PowShape S = pow_var();  // pow16_powp's shape
   const FbTab G = c->gtab->tab();
   const uint32_t *sched = nullptr, *jobs = nullptr;
   uint8_t *d_base = nullptr, *d_exp = nullptr, *d_out = nullptr;

@@ -67,7 +67,7 @@ static int hash_chunk_locked(eg_ctx* c, const ManShape& M, size_t nbc, const uin
   if (!hc && (rc = ws_get(c, W_OK1, ncn * 32, (void**)&hc))) return rc;
   std::vector<const uint32_t*> jv;
   if ((rc = cached_job_set(c, "ch/" + M.key, {"first", "spc"},
-                           [&]() { return std::vector<std::vector<uint32_t>>{M.first, M.spc}; }, jv)))
+                           [&]() { return JobSet{M.first, M.spc}; }, jv)))
     return rc;
   hipLaunchKernelGGL(k_sel_hash, dim3(cgrid(ns)), dim3(256), 0, c->stream, c->d_q, d_dsel, d_cts, (uint64_t)ns,
                      (uint32_t)nsel, hs, c->hash_fmt);

@@ -46,7 +46,6 @@ extern "C" int eg_decrypt2_commit(eg_ctx* c, const uint8_t secret_be[32], const 
   // g's shared comb table first: building it runs its own job through W_JOBS / W_SCR
   const uint32_t* gc = nullptr;
   if ((rc = g_comb_table(c, &gc))) return rc;
-  const FbTab G = c->gtab->tab();
   const size_t ch = d2_chunk(1);
   for (size_t i0 = 0; i0 < n; i0 += ch) {
     const size_t m = std::min(ch, n - i0);
@@ -59,25 +58,9 @@ extern "C" int eg_decrypt2_commit(eg_ctx* c, const uint8_t secret_be[32], const 
     if ((rc = ws_get(c, W_E0, m * kW * 4, (void**)&E))) return rc;
     if ((rc = launch_import(c, d_t, m, E, nullptr))) return rc;
     if ((rc = ws_get(c, W_E1, m * 3 * kW * 4, (void**)&O))) return rc;
-    auto JA = new_jobs(m), JB = new_jobs(m);
-    for (size_t i = 0; i < m; ++i) {
-      uint32_t* a = &JA[i * kJobWords];  // M = A^z (out 3 i), b = A^u (out 3 i + 2)
-      a[0] = (uint32_t)i; a[1] = 0; a[2] = (uint32_t)(1 + i); a[3] = (uint32_t)(i * 3); a[4] = (uint32_t)(i * 3 + 2);
-      uint32_t* b = &JB[i * kJobWords];  // a = g^u (out 3 i + 1)
-      b[0] = 0; b[1] = (uint32_t)(1 + i); b[3] = (uint32_t)(i * 3 + 1);
-    }
-    const uint32_t *ja, *jb;
-    if ((rc = upload_jobs(c, W_JOBS, JA, &ja)) || (rc = upload_jobs(c, W_H1, JB, &jb))) return rc;
-    // eg_trustee_decrypt_batch's launch: z and u only ever drive the constant-time comb
-    // (k_pow<F, true>: fixed schedule, every table read a masked scan of the whole table)
-    {
-      PowShape S{};
-      S.has_base = 1; S.nout = 2; S.exp_bytes = 32; S.comb = 1; S.rows = c->ct_rows; S.blocks = c->ct_rows == 4 ? 2u : 0u;
-      PowTail T{};
-      T.S.has_base = 1; T.S.nout = 1; T.S.exp_bytes = 32; T.S.comb = 1; T.S.shared_comb = 1;
-      T.jobs = jb; T.njobs = m; T.ctab = gc;
-      if ((rc = launch_pow(c, S, ja, m, E, SC, O, G, G, nullptr, nullptr, &T, nullptr, true))) return rc;
-    }
+    // M = A^z (out 3 i), a = g^u (out 3 i + 1), b = A^u (out 3 i + 2): z and u only ever drive the
+    // constant-time comb
+    if ((rc = trustee_pair_launch(c, gc, E, 1, SC, m, O))) return rc;
     if ((rc = ws_get(c, W_BE0, m * 3 * 512, (void**)&OBE))) return rc;
     if ((rc = launch_export(c, O, m * 3, OBE))) return rc;
     HIPCHK(hipMemcpy2DAsync(out_M + i0 * 512, 512, OBE, 1536, 512, m, hipMemcpyDeviceToHost, c->stream));
@@ -227,43 +210,17 @@ static int d2_check_chunk_locked(eg_ctx* c, size_t m, size_t k, const uint8_t* d
   hipLaunchKernelGGL(k_d2_range, dim3(cgrid(N)), dim3(kBlock), 0, c->stream, c->d_q, ci, vi, 32u, (uint64_t)N, OKR);
   HIPCHK(hipGetLastError());
   if ((rc = ws_get(c, W_E1, 4 * N * kW * 4, (void**)&O))) return rc;
-  auto JA = new_jobs(N), JB = new_jobs(N), JC = new_jobs(N);
-  for (size_t t = 0; t < m; ++t)
-    for (size_t i = 0; i < k; ++i) {
-      const size_t j = t * k + i;
-      const uint32_t cc = (uint32_t)j, vv = (uint32_t)(N + j);
-      // a = Z_i^{c_i} g^{v_i}; with tables the jobs are guardian-major, one launch per table
-      uint32_t* a = &JA[(tabs ? i * m + t : j) * kJobWords];
-      a[3] = (uint32_t)(2 * j); a[5] = vv;
-      if (tabs) a[6] = cc;
-      else a[0] = (uint32_t)i, a[1] = cc;
-      uint32_t* b = &JB[j * kJobWords];  // A^{v_i}
-      b[0] = (uint32_t)(oT + 2 * t); b[1] = vv; b[3] = (uint32_t)(2 * N + 2 * j);
-      uint32_t* d = &JC[j * kJobWords];  // M_i^{c_i}
-      d[0] = (uint32_t)(oS + j); d[1] = cc; d[3] = (uint32_t)(2 * N + 2 * j + 1);
-    }
-  const uint32_t *ja, *jb, *jc;
-  if ((rc = upload_jobs(c, W_JOBS, JA, &ja)) || (rc = upload_jobs(c, W_H1, JB, &jb)) ||
-      (rc = upload_jobs(c, W_H2, JC, &jc)))
-    return rc;
-  const FbTab G = c->gtab->tab();
-  PowShape S1{};
-  if (tabs) {  // g^v (fb0) * Z_i^c (fb1)
-    S1.nout = 1; S1.nfb[0] = 2; S1.exp_bytes = 32; S1.tab[0][0] = 0; S1.tab[0][1] = 1;
-    for (size_t i = 0; i < k; ++i)
-      if ((rc = launch_pow(c, S1, ja + i * m * kJobWords, m, E, SC, O, G, kt[i]->tab()))) return rc;
-  } else {
-    S1.has_base = 1; S1.nout = 1; S1.nfb[0] = 1; S1.exp_bytes = 32;
-    if ((rc = launch_pow(c, S1, ja, N, E, SC, O, G, G))) return rc;
-  }
-  PowShape S2{};
-  S2.has_base = 1; S2.nout = 1; S2.exp_bytes = 32;
-  if ((rc = launch_pow(c, S2, jb, N, E, SC, O, G, G))) return rc;
-  if ((rc = launch_pow(c, S2, jc, N, E, SC, O, G, G))) return rc;
-  LAUNCH_F(c, k_mul, dim3(grid_for(N)), c->d, O + 2 * N * kW, 2u, O + (2 * N + 1) * kW, 2u, (uint32_t)N, O + kW, 2u);
-  HIPCHK(hipGetLastError());
   if ((rc = ws_get(c, W_BE0, 2 * N * 512, (void**)&OBE))) return rc;
-  if ((rc = launch_export(c, O, 2 * N, OBE))) return rc;
+  // elements [Z (k)][A, B (2 m)][M_i (N)], scalars [c_i (N)][v_i (N)]; Z_i a variable base
+  // (item j's is element j % k) unless the guardians' tables are given; outputs: pairs
+  // a = Z_i^{c_i} g^{v_i}, b = A^{v_i} M_i^{c_i}, the factors of b behind them
+  CpLayout CP{};
+  CP.n = N; CP.k = k;
+  CP.eX = 0; CP.nX = (uint32_t)k; CP.eA = (uint32_t)oT; CP.eM = (uint32_t)oS;
+  CP.sC = 0; CP.sV = (uint32_t)N; CP.ds = 1; CP.sNeg = kNone;
+  CP.so = 2; CP.oT = (uint32_t)(2 * N); CP.dT = 2;
+  for (eg_fixed_base* t : kt) CP.tabs.push_back(t->tab());
+  if ((rc = cp_recompute(c, CP, E, SC, O, OBE))) return rc;
   hipLaunchKernelGGL(k_d2_match, dim3(cgrid(N)), dim3(kBlock), 0, c->stream, OBE, comm, OKR, (uint64_t)N, ok);
   hipLaunchKernelGGL(k_d2_vsum, dim3(cgrid(m)), dim3(kBlock), 0, c->stream, c->d_q, vi, (uint64_t)m, (uint32_t)k, out_v);
   HIPCHK(hipGetLastError());
@@ -336,32 +293,16 @@ static int d2_verify_chunk_locked(eg_ctx* c, size_t m, const uint8_t* CN, const 
                      (uint64_t)m, OKR);
   HIPCHK(hipGetLastError());
   if ((rc = ws_get(c, W_E1, 4 * m * kW * 4, (void**)&O))) return rc;
-  auto JA = new_jobs(m), JB = new_jobs(m), JC = new_jobs(m);
-  for (size_t i = 0; i < m; ++i) {
-    const uint32_t cc = (uint32_t)(2 * i), vv = cc + 1;
-    uint32_t* a = &JA[i * kJobWords];  // a' = g^v K^c
-    a[3] = (uint32_t)(2 * i); a[5] = vv; a[6] = cc;
-    uint32_t* b = &JB[i * kJobWords];  // A^v
-    b[0] = (uint32_t)(2 * i); b[1] = vv; b[3] = (uint32_t)(2 * m + 2 * i);
-    uint32_t* d = &JC[i * kJobWords];  // M^c
-    d[0] = (uint32_t)(2 * m + i); d[1] = cc; d[3] = (uint32_t)(2 * m + 2 * i + 1);
-  }
-  const uint32_t *ja, *jb, *jc;
-  if ((rc = upload_jobs(c, W_JOBS, JA, &ja)) || (rc = upload_jobs(c, W_H1, JB, &jb)) ||
-      (rc = upload_jobs(c, W_H2, JC, &jc)))
-    return rc;
-  const FbTab G = c->gtab->tab();
-  PowShape S1{};
-  S1.nout = 1; S1.nfb[0] = 2; S1.exp_bytes = 32; S1.tab[0][0] = 0; S1.tab[0][1] = 1;
-  if ((rc = launch_pow(c, S1, ja, m, E, SC, O, G, c->Ktab->tab()))) return rc;
-  PowShape S2{};
-  S2.has_base = 1; S2.nout = 1; S2.exp_bytes = 32;
-  if ((rc = launch_pow(c, S2, jb, m, E, SC, O, G, G))) return rc;
-  if ((rc = launch_pow(c, S2, jc, m, E, SC, O, G, G))) return rc;
-  LAUNCH_F(c, k_mul, dim3(grid_for(m)), c->d, O + 2 * m * kW, 2u, O + (2 * m + 1) * kW, 2u, (uint32_t)m, O + kW, 2u);
-  HIPCHK(hipGetLastError());
   if ((rc = ws_get(c, W_BE0, 2 * m * 512, (void**)&OBE))) return rc;
-  if ((rc = launch_export(c, O, 2 * m, OBE))) return rc;
+  // elements [A, B (2 m)][M (m)], scalars the proof rows (c, v); the key is K's table, so no
+  // X elements (eX, nX unused); outputs: pairs a' = g^v K^c, b' = A^v M^c, b's factors behind them
+  CpLayout CP{};
+  CP.n = m; CP.k = 1;
+  CP.eA = 0; CP.eM = (uint32_t)(2 * m);
+  CP.sC = 0; CP.sV = 1; CP.ds = 2; CP.sNeg = kNone;
+  CP.so = 2; CP.oT = (uint32_t)(2 * m); CP.dT = 2;
+  CP.tabs = {c->Ktab->tab()};
+  if ((rc = cp_recompute(c, CP, E, SC, O, OBE))) return rc;
   return launch_hash(c, (uint32_t)m,
                      {HashSrc{CN, 32, 0}, key_src(c), HashSrc{texts, 512, 1024}, HashSrc{texts + 512, 512, 1024},
                       HashSrc{OBE, 512, 1024}, HashSrc{OBE + 512, 512, 1024}, HashSrc{M, 512, 512}},

@@ -80,11 +80,12 @@ static PreShape pre_shape(size_t nc, const uint32_t* spc, const uint32_t* limits
 static size_t pre_chunk(size_t per_ballot) { return std::max<size_t>(1, EG_PRE_CHUNK_CTS / per_ballot); }
 
 // n component jobs: (alpha, beta) -> elements 2i, 2i + 1; rho is scalar i, [i = j] scalar n + i
-static std::vector<uint32_t> pre_jobs(size_t n) {
+static std::vector<PowJob> pre_jobs(size_t n) {
   auto J = new_jobs(n);
   for (size_t i = 0; i < n; ++i) {
-    uint32_t* j = &J[i * kJobWords];
-    j[3] = (uint32_t)(2 * i); j[4] = j[3] + 1; j[5] = (uint32_t)i; j[7] = (uint32_t)i; j[8] = (uint32_t)(n + i);
+    PowJob& j = J[i];
+    j.out[0] = (uint32_t)(2 * i); j.out[1] = j.out[0] + 1;
+    j.fb[0][0] = (uint32_t)i; j.fb[1][0] = (uint32_t)i; j.fb[1][1] = (uint32_t)(n + i);
   }
   return J;
 }
@@ -94,10 +95,9 @@ static int pre_pow_locked(eg_ctx* c, const uint32_t* jobs, size_t n, const uint8
   int rc;
   FbTab G{}, K{};
   if ((rc = enc_tables_locked(c, &G, &K))) return rc;
-  PowShape S{};
-  S.nout = 2; S.nfb[0] = 1; S.nfb[1] = 2; S.exp_bytes = 32; S.tab[1][0] = 1; S.tab[1][1] = 0;
-  S.fb_small[1][1] = 1;
-  return launch_pow(c, S, jobs, n, U, SC, U, G, K, nullptr, nullptr, nullptr, nullptr, c->ct_encrypt != 0);
+  PowShape S = pow_fb_pair(true);
+  S.fb_small[1][1] = 1;  // [i = j] is 0 or 1: one window of g's table
+  return launch_pow(c, {S, jobs, n}, U, SC, U, G, K, pow_ct(c->ct_encrypt != 0));
 }
 
 // psi of vectors whose components are consecutive ciphertexts: cts (nbc * per * 1024 B) ->
@@ -150,7 +150,7 @@ static int pre_chunk_locked(eg_ctx* c, const PreShape& P, size_t nbc, uint32_t c
   std::vector<const uint32_t*> tv;
   rc = cached_job_set(c, "pe/" + std::to_string(nbc) + "/" + P.key, {"diag", "vfirst", "vlen", "kof", "off", "spc", "jobs"},
                       [&]() {
-                        return std::vector<std::vector<uint32_t>>{P.diag, P.vfirst, P.vlen, P.kof, P.M.first, P.M.spc,
+                        return JobSet{P.diag, P.vfirst, P.vlen, P.kof, P.M.first, P.M.spc,
                                                                   pre_jobs(n)};
                       }, tv);
   if (rc) return rc;
@@ -236,7 +236,7 @@ static int record_chunk_locked(eg_ctx* c, const PreShape& P, size_t nbc, uint32_
   rc = cached_job_set(c, "pr/" + std::to_string(nbc) + "/" + P.key,
                       {"uk", "ul", "off", "spc", "voff", "soff", "toff", "limit", "tfirst", "tlen", "tk", "kof", "jobs"},
                       [&]() {
-                        return std::vector<std::vector<uint32_t>>{P.uk, P.ul, P.M.first, P.M.spc, P.voff, P.soff,
+                        return JobSet{P.uk, P.ul, P.M.first, P.M.spc, P.voff, P.soff,
                                                                   P.toff, P.M.limit, P.tfirst, P.tlen, P.tk, P.kof,
                                                                   pre_jobs(n)};
                       }, tv);
@@ -344,7 +344,7 @@ static int preverify_chunk_locked(eg_ctx* c, const PreShape& P, size_t nbc, uint
     for (const char* nm : {"in", "out"}) names.push_back(nm + std::to_string(ci));
   std::vector<const uint32_t*> tv;
   rc = cached_job_set(c, "pv/" + P.key, names, [&]() {
-    std::vector<std::vector<uint32_t>> out{P.M.first, P.M.spc, P.soff, P.toff, P.M.limit, P.tfirst, P.tlen, P.tk};
+    JobSet out{P.M.first, P.M.spc, P.soff, P.toff, P.M.limit, P.tfirst, P.tlen, P.tk};
     for (const auto& members : cls) {  // group (k, j, comp): chosen rows soff_k + j (+ t spc_k) -> slot off_k + j
       std::vector<uint32_t> in, ot;
       for (uint32_t k : members)

@@ -64,42 +64,38 @@ static int range_verify_chunk_locked(eg_ctx* c, size_t n, uint32_t L, const uint
     auto A = new_jobs(n), Bj = new_jobs(n), XA = new_jobs(nx), XB = new_jobs(nx);
     for (size_t i = 0; i < n; ++i) {
       const uint32_t s0 = (uint32_t)(i * 2 * B), o0 = (uint32_t)(i * 2 * B);  // scalar / commitment row of item i
-      uint32_t* a = &A[i * kJobWords];
-      uint32_t* b = &Bj[i * kJobWords];
-      a[0] = (uint32_t)(i * 2); a[1] = s0; a[2] = s0 + 2; a[3] = o0; a[4] = o0 + 2; a[5] = s0 + 1; a[7] = s0 + 3;
-      b[0] = (uint32_t)(i * 2 + 1); b[1] = s0; b[2] = s0 + 2; b[3] = o0 + 1; b[4] = o0 + 3; b[5] = s0 + 1;
-      b[7] = s0 + 3; b[8] = (uint32_t)(off_g + i * B + 1);
+      PowJob& a = A[i];
+      PowJob& b = Bj[i];
+      a.base = (uint32_t)(i * 2); a.exp[0] = s0; a.exp[1] = s0 + 2; a.out[0] = o0; a.out[1] = o0 + 2;
+      a.fb[0][0] = s0 + 1; a.fb[1][0] = s0 + 3;
+      b.base = (uint32_t)(i * 2 + 1); b.exp[0] = s0; b.exp[1] = s0 + 2; b.out[0] = o0 + 1; b.out[1] = o0 + 3;
+      b.fb[0][0] = s0 + 1; b.fb[1][0] = s0 + 3; b.fb[1][1] = (uint32_t)(off_g + i * B + 1);
       for (size_t j = 2; j < B; ++j) {
-        uint32_t* xa = &XA[(i * (B - 2) + (j - 2)) * kJobWords];
-        uint32_t* xb = &XB[(i * (B - 2) + (j - 2)) * kJobWords];
+        PowJob& xa = XA[i * (B - 2) + (j - 2)];
+        PowJob& xb = XB[i * (B - 2) + (j - 2)];
         const uint32_t cj = s0 + (uint32_t)(2 * j), vj = cj + 1;
-        xa[0] = (uint32_t)(i * 2); xa[1] = cj; xa[2] = (uint32_t)i; xa[3] = o0 + (uint32_t)(2 * j); xa[5] = vj;
-        xb[0] = (uint32_t)(i * 2 + 1); xb[1] = cj; xb[2] = (uint32_t)i; xb[3] = o0 + (uint32_t)(2 * j + 1); xb[5] = vj;
-        xb[6] = (uint32_t)(off_g + i * B + j);
+        xa.base = (uint32_t)(i * 2); xa.exp[0] = cj; xa.gather_src() = (uint32_t)i;
+        xa.out[0] = o0 + (uint32_t)(2 * j); xa.fb[0][0] = vj;
+        xb.base = (uint32_t)(i * 2 + 1); xb.exp[0] = cj; xb.gather_src() = (uint32_t)i;
+        xb.out[0] = o0 + (uint32_t)(2 * j + 1); xb.fb[0][0] = vj; xb.fb[0][1] = (uint32_t)(off_g + i * B + j);
       }
     }
-    return std::vector<std::vector<uint32_t>>{std::move(A), std::move(Bj), std::move(XA), std::move(XB)};
+    return JobSet{std::move(A), std::move(Bj), std::move(XA), std::move(XB)};
   }, jv);
   if (rc) return rc;
   const bool gat = c->use_comb != 0;
-  PowShape SA{};  // a_0 = alpha^e0 g^v0, a_1 = alpha^e1 g^v1 (the selection verifier's alpha shape)
-  SA.has_base = 1; SA.nout = 2; SA.nfb[0] = 1; SA.nfb[1] = 1; SA.exp_bytes = 32; SA.comb = 1; SA.resid = 1;
-  SA.rows = c->sel_rows; SA.blocks = c->sel_blocks;
-  PowShape SB = SA;  // b_0 = beta^e0 K^v0, b_1 = beta^e1 K^v1 g^-e1
-  SB.nfb[1] = 2; SB.tab[0][0] = 1; SB.tab[1][0] = 1; SB.tab[1][1] = 0;
-  PowShape XA{};  // a_j = alpha^ej g^vj on the pair job's comb powers
-  XA.has_base = 1; XA.nout = 1; XA.nfb[0] = 1; XA.exp_bytes = 32; XA.comb = gat ? 1u : 0u; XA.gather = gat ? 1u : 0u;
-  PowShape XB = XA;  // b_j = beta^ej K^vj g^(-j ej)
-  XB.nfb[0] = 2; XB.tab[0][0] = 1; XB.tab[0][1] = 0;
-  {
-    PowTail T{};  // the beta pair jobs ride in the alpha launch's last sub-launch
-    T.S = SB; T.jobs = jv[1]; T.njobs = n; T.yout = gat ? YB : nullptr; T.rout = RZ + n * 2 * kW;
-    if ((rc = launch_pow(c, SA, jv[0], n, E, SC, COMM, G, K, gat ? YA : nullptr, nullptr, &T, RZ))) return rc;
-  }
+  // the selection verifier's shapes: a_0 = alpha^e0 g^v0, a_1 = alpha^e1 g^v1 and
+  // b_0 = beta^e0 K^v0, b_1 = beta^e1 K^v1 g^-e1; the beta pair jobs ride in the alpha launch's
+  // last sub-launch
+  const PowPop PA{pow_sel_pair(false, c->sel_rows, c->sel_blocks), jv[0], n, gat ? YA : nullptr, nullptr, RZ};
+  const PowPop PB{pow_sel_pair(true, c->sel_rows, c->sel_blocks), jv[1], n, gat ? YB : nullptr, nullptr,
+                  RZ + n * 2 * kW};
+  if ((rc = launch_pow(c, PA, E, SC, COMM, G, K, {PB}))) return rc;
   if (nx) {
-    PowTail T{};
-    T.S = XB; T.jobs = jv[3]; T.njobs = nx; T.ygat = YB;
-    if ((rc = launch_pow(c, XA, jv[2], nx, E, SC, COMM, G, K, nullptr, YA, &T))) return rc;
+    // a_j = alpha^ej g^vj and b_j = beta^ej K^vj g^(-j ej) on the pair job's comb powers
+    const PowPop XA{pow_sel_gather(false, gat ? 1u : 0u), jv[2], nx, nullptr, YA};
+    const PowPop XB{pow_sel_gather(true, gat ? 1u : 0u), jv[3], nx, nullptr, YB};
+    if ((rc = launch_pow(c, XA, E, SC, COMM, G, K, {XB}))) return rc;
   }
   // alpha^q == 1 and beta^q == 1 fold into the range flags.  From here on LTP (W_FLAGS) holds, for
   // item i of this call, its alpha's flag at [2 i] and its beta's at [2 i + 1]: range (k_import)
@@ -178,25 +174,20 @@ static int range_prove_chunk_locked(eg_ctx* c, size_t n, uint32_t L, const uint8
     auto S = new_jobs(n * B), Rj = new_jobs(n);
     for (size_t i = 0; i < n; ++i) {
       for (size_t j = 0; j < B; ++j) {
-        uint32_t* s = &S[(i * B + j) * kJobWords];  // a_j = g^s_j ; b_j = K^s_j g^t_j
+        PowJob& s = S[i * B + j];  // a_j = g^s_j ; b_j = K^s_j g^t_j
         const uint32_t sj = (uint32_t)(off_s + i * B + j);
-        s[3] = (uint32_t)(i * 2 * B + 2 * j); s[4] = s[3] + 1; s[5] = sj; s[7] = sj;
-        s[8] = (uint32_t)(off_t + i * B + j);
+        s.out[0] = (uint32_t)(i * 2 * B + 2 * j); s.out[1] = s.out[0] + 1; s.fb[0][0] = sj; s.fb[1][0] = sj;
+        s.fb[1][1] = (uint32_t)(off_t + i * B + j);
       }
-      uint32_t* r = &Rj[i * kJobWords];  // g^u ; K^u
-      r[3] = (uint32_t)(oRE + i * 2); r[4] = r[3] + 1; r[5] = (uint32_t)(i * nw); r[7] = r[5];
+      PowJob& r = Rj[i];  // g^u ; K^u
+      r.out[0] = (uint32_t)(oRE + i * 2); r.out[1] = r.out[0] + 1; r.fb[0][0] = (uint32_t)(i * nw); r.fb[1][0] = r.fb[0][0];
     }
-    return std::vector<std::vector<uint32_t>>{std::move(S), std::move(Rj)};
+    return JobSet{std::move(S), std::move(Rj)};
   }, jv);
   if (rc) return rc;
-  {
-    PowShape S{};
-    S.nout = 2; S.nfb[0] = 1; S.nfb[1] = 2; S.exp_bytes = 32; S.tab[1][0] = 1; S.tab[1][1] = 0;
-    PowTail T{};  // the real pairs fill the simulated pairs' last round
-    T.S.nout = 2; T.S.nfb[0] = 1; T.S.nfb[1] = 1; T.S.exp_bytes = 32; T.S.tab[1][0] = 1;
-    T.jobs = jv[1]; T.njobs = n;
-    if ((rc = launch_pow(c, S, jv[0], n * B, U, SC, U, G, K, nullptr, nullptr, &T, nullptr, ct))) return rc;
-  }
+  // the real pairs fill the simulated pairs' last round
+  if ((rc = launch_pow(c, {pow_fb_pair(true), jv[0], n * B}, U, SC, U, G, K, {{pow_fb_pair(false), jv[1], n}, {}, ct})))
+    return rc;
   constexpr size_t kQuads = 2 * kW / 4;
   hipLaunchKernelGGL(k_range_order, dim3(cgrid(n * kQuads)), dim3(kBlock), 0, c->stream, U, U + oRE * kW, d_values,
                      (uint64_t)n, L);

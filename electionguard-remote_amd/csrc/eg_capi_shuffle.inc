@@ -77,16 +77,12 @@ static int sh_generators(eg_ctx* c, bool host, const uint8_t* cof_be, const uint
   if ((rc = launch_import(c, X, n1, EL, nullptr))) return rc;  // an X_k >= p is reduced
   auto J = new_jobs(n1);
   for (size_t i = 0; i < n1; ++i) {
-    uint32_t* a = &J[i * kJobWords];  // X_i^cof: every job reads the one 512-byte exponent
-    a[0] = (uint32_t)i; a[1] = 0; a[3] = (uint32_t)i;
+    PowJob& a = J[i];  // X_i^cof: every job reads the one 512-byte exponent
+    a.base = (uint32_t)i; a.exp[0] = 0; a.out[0] = (uint32_t)i;
   }
-  const uint32_t* dj = nullptr;
-  if ((rc = upload_jobs(c, W_SH_JOBS, J, &dj))) return rc;
   if ((rc = ws_get(c, W_SH_O, (N + 2) * E, (void**)&O))) return rc;
-  PowShape S{};
-  S.has_base = 1; S.nout = 1; S.exp_bytes = 512;
   const FbTab Gt = c->gtab->tab();
-  if ((rc = launch_pow(c, S, dj, n1, EL, CN + 32, O, Gt, Gt))) return rc;
+  if ((rc = launch_pow_jobs(c, W_SH_JOBS, pow_var(1, 512), J, EL, CN + 32, O, Gt, Gt))) return rc;
   if ((rc = run_prod(c, O + kW, GroupMap{1, 1, 0, 0, (uint32_t)N}, 1, N, 1, O + n1 * kW))) return rc;
   uint8_t* GB = host ? X : G;  // the digests are dead after the import
   if ((rc = launch_export(c, O, N + 2, GB))) return rc;
@@ -144,15 +140,12 @@ static int sh_mix(eg_ctx* c, bool host, const uint8_t* K_be, size_t N, size_t w,
   if ((rc = launch_import(c, d_E, items, EL, nullptr))) return rc;
   auto J = new_jobs(cells);
   for (size_t i = 0; i < cells; ++i) {
-    uint32_t* a = &J[i * kJobWords];  // g^r (out 2 i) and K^r (out 2 i + 1)
-    a[3] = (uint32_t)(2 * i); a[4] = (uint32_t)(2 * i + 1); a[5] = (uint32_t)i; a[7] = (uint32_t)i;
+    PowJob& a = J[i];  // g^r (out 2 i) and K^r (out 2 i + 1)
+    a.out[0] = (uint32_t)(2 * i); a.out[1] = (uint32_t)(2 * i + 1); a.fb[0][0] = (uint32_t)i; a.fb[1][0] = (uint32_t)i;
   }
-  const uint32_t* dj = nullptr;
-  if ((rc = upload_jobs(c, W_SH_JOBS, J, &dj))) return rc;
   if ((rc = ws_get(c, W_SH_O, items * E, (void**)&O))) return rc;
-  PowShape S{};
-  S.nout = 2; S.nfb[0] = 1; S.nfb[1] = 1; S.exp_bytes = 32; S.tab[0][0] = 0; S.tab[1][0] = 1;
-  if ((rc = launch_pow(c, S, dj, cells, nullptr, SC, O, c->gtab->tab(), c->Ktab->tab()))) return rc;
+  if ((rc = launch_pow_jobs(c, W_SH_JOBS, pow_fb_pair(false), J, nullptr, SC, O, c->gtab->tab(), c->Ktab->tab())))
+    return rc;
   // row i of the output takes row psi(i) of the input: in place over the powers
   LAUNCH_F(c, k_sh_gather_mul, dim3(grid_for(items)), c->d, EL, d_psi, (uint32_t)N, (uint32_t)(2 * w), O,
            (uint64_t)items, O);
@@ -326,21 +319,6 @@ static int sh_scan(eg_ctx* c, uint8_t* A, uint8_t* B, size_t n, uint8_t* T) {
   return EG_OK;
 }
 
-static int sh_pow(eg_ctx* c, const PowShape& S, const std::vector<uint32_t>& J, const uint32_t* elems,
-                  const uint8_t* scal, uint32_t* out, FbTab f0, FbTab f1) {
-  const uint32_t* dj = nullptr;
-  int rc = upload_jobs(c, W_SH_JOBS, J, &dj);
-  if (rc) return rc;
-  return launch_pow(c, S, dj, J.size() / kJobWords, elems, scal, out, f0, f1);
-}
-
-static PowShape sh_shape(bool base, uint32_t nfb0, uint32_t nout = 1) {
-  PowShape S{};
-  S.has_base = base ? 1 : 0; S.nout = nout; S.nfb[0] = nfb0; S.exp_bytes = 32;
-  if (nout == 2) S.nfb[1] = 1, S.tab[1][0] = 1;
-  return S;
-}
-
 static int sh_reduce(eg_ctx* c, const uint8_t* in, size_t n, uint8_t* out) {
   hipLaunchKernelGGL(k_sh_reduce, dim3(cgrid(n)), dim3(kBlock), 0, c->stream, c->d_q, in, (uint64_t)n, out);
   HIPCHK(hipGetLastError());
@@ -409,8 +387,8 @@ static int sh_prove_locked(eg_ctx* c, const uint8_t* CN, size_t N, size_t w, con
   if ((rc = ws_get(c, W_SH_O, N * E, (void**)&O1)) || (rc = ws_get(c, W_SH_PSI2, N * 4, (void**)&INV))) return rc;
   {
     auto J = new_jobs(N);
-    for (size_t j = 0; j < N; ++j) J[j * kJobWords + 3] = (uint32_t)j, J[j * kJobWords + 5] = (uint32_t)(iRho + j);
-    if ((rc = sh_pow(c, sh_shape(false, 1), J, nullptr, SC, O1, Gt, Gt))) return rc;
+    for (size_t j = 0; j < N; ++j) J[j].out[0] = (uint32_t)j, J[j].fb[0][0] = (uint32_t)(iRho + j);
+    if ((rc = launch_pow_jobs(c, W_SH_JOBS, pow_fb_one(), J, nullptr, SC, O1, Gt, Gt))) return rc;
   }
   HIPCHK(hipMemsetAsync(INV, 0, N * 4, c->stream));
   hipLaunchKernelGGL(k_sh_invert, dim3(cgrid(N)), dim3(kBlock), 0, c->stream, psi, (uint64_t)N, INV);
@@ -434,10 +412,10 @@ static int sh_prove_locked(eg_ctx* c, const uint8_t* CN, size_t N, size_t w, con
   {
     auto J = new_jobs(N);
     for (size_t i = 0; i < N; ++i) {
-      uint32_t* a = &J[i * kJobWords];
-      a[0] = 0; a[1] = (uint32_t)(iUU + i); a[3] = (uint32_t)(1 + i); a[5] = (uint32_t)(iR + i);
+      PowJob& a = J[i];
+      a.base = 0; a.exp[0] = (uint32_t)(iUU + i); a.out[0] = (uint32_t)(1 + i); a.fb[0][0] = (uint32_t)(iR + i);
     }
-    if ((rc = sh_pow(c, sh_shape(true, 1), J, EG, SC, O2, Gt, Gt))) return rc;
+    if ((rc = launch_pow_jobs(c, W_SH_JOBS, pow_var(1, 32, 1), J, EG, SC, O2, Gt, Gt))) return rc;
   }
   if ((rc = launch_export(c, O2 + kW, N, o_chain))) return rc;
   // witnesses
@@ -452,14 +430,14 @@ static int sh_prove_locked(eg_ctx* c, const uint8_t* CN, size_t N, size_t w, con
   {
     auto J = new_jobs(3);
     const uint32_t outs[3] = {0, 1, (uint32_t)oF};
-    for (int k = 0; k < 3; ++k) J[k * kJobWords + 3] = outs[k], J[k * kJobWords + 5] = (uint32_t)(iOm + k);
-    if ((rc = sh_pow(c, sh_shape(false, 1), J, nullptr, SC, TX, Gt, Gt))) return rc;
+    for (int k = 0; k < 3; ++k) J[k].out[0] = outs[k], J[k].fb[0][0] = (uint32_t)(iOm + k);
+    if ((rc = launch_pow_jobs(c, W_SH_JOBS, pow_fb_one(), J, nullptr, SC, TX, Gt, Gt))) return rc;
     auto J4 = new_jobs(w);
     for (size_t j = 0; j < w; ++j) {
-      uint32_t* a = &J4[j * kJobWords];
-      a[3] = (uint32_t)(oF + 1 + 2 * j); a[4] = a[3] + 1; a[5] = (uint32_t)(iNW4 + j); a[7] = a[5];
+      PowJob& a = J4[j];
+      a.out[0] = (uint32_t)(oF + 1 + 2 * j); a.out[1] = a.out[0] + 1; a.fb[0][0] = (uint32_t)(iNW4 + j); a.fb[1][0] = a.fb[0][0];
     }
-    if ((rc = sh_pow(c, sh_shape(false, 1, 2), J4, nullptr, SC, TX, Gt, Kt))) return rc;
+    if ((rc = launch_pow_jobs(c, W_SH_JOBS, pow_fb_pair(false), J4, nullptr, SC, TX, Gt, Kt))) return rc;
   }
   if ((rc = sh_pp(c, G + 512, N, 1, sc(iOmP), 1, N, TX + oP * kW))) return rc;
   if ((rc = sh_pp(c, E2, 1, 2 * w, sc(iOmP), 2 * w, N, TX + (oP + 1) * kW))) return rc;
@@ -471,10 +449,10 @@ static int sh_prove_locked(eg_ctx* c, const uint8_t* CN, size_t N, size_t w, con
   {
     auto J = new_jobs(N);
     for (size_t i = 0; i < N; ++i) {
-      uint32_t* a = &J[i * kJobWords];
-      a[0] = (uint32_t)i; a[1] = (uint32_t)(iOmP + i); a[3] = (uint32_t)i; a[5] = (uint32_t)(iOmH + i);
+      PowJob& a = J[i];
+      a.base = (uint32_t)i; a.exp[0] = (uint32_t)(iOmP + i); a.out[0] = (uint32_t)i; a.fb[0][0] = (uint32_t)(iOmH + i);
     }
-    if ((rc = sh_pow(c, sh_shape(true, 1), J, O2, SC, O3, Gt, Gt))) return rc;
+    if ((rc = launch_pow_jobs(c, W_SH_JOBS, pow_var(1, 32, 1), J, O2, SC, O3, Gt, Gt))) return rc;
   }
   if ((rc = ws_get(c, W_SH_BE2, N * 512, (void**)&BE2))) return rc;
   if ((rc = launch_export(c, O3, N, BE2))) return rc;
@@ -566,8 +544,8 @@ static int sh_residues(eg_ctx* c, const uint8_t* CN, const uint8_t* els, size_t 
     return rc;
   auto J = new_jobs(ch);
   for (size_t i = 0; i < ch; ++i) {
-    uint32_t* a = &J[i * kJobWords];
-    a[0] = (uint32_t)i; a[1] = 0; a[3] = (uint32_t)i;
+    PowJob& a = J[i];
+    a.base = (uint32_t)i; a.exp[0] = 0; a.out[0] = (uint32_t)i;
   }
   const uint32_t* dj = nullptr;
   if ((rc = upload_jobs(c, W_SH_JOBS, J, &dj))) return rc;
@@ -575,7 +553,7 @@ static int sh_residues(eg_ctx* c, const uint8_t* CN, const uint8_t* els, size_t 
   for (size_t i0 = 0; i0 < n; i0 += ch) {
     const size_t m = std::min(ch, n - i0);
     if ((rc = launch_import(c, els + i0 * 512, m, RE, LT))) return rc;
-    if ((rc = launch_pow(c, sh_shape(true, 0), dj, m, RE, CN + kShQ * 32, RO, Gt, Gt))) return rc;
+    if ((rc = launch_pow(c, {pow_var(), dj, m}, RE, CN + kShQ * 32, RO, Gt, Gt))) return rc;
     if ((rc = launch_export(c, RO, m, RB))) return rc;
     hipLaunchKernelGGL(k_sh_resid, dim3(cgrid(m)), dim3(kBlock), 0, c->stream, RB, LT, (uint64_t)m, flag);
     HIPCHK(hipGetLastError());
@@ -634,9 +612,9 @@ static int sh_verify_locked(eg_ctx* c, const uint8_t* CN, size_t N, size_t w, co
   if ((rc = run_prod(c, V + vP * kW, GroupMap{1, 1, 0, 0, (uint32_t)N}, 1, N, 1, W + wT * kW))) return rc;
   {
     auto J = new_jobs(2);
-    J[0] = (uint32_t)(N + 1); J[1] = (uint32_t)iQm1; J[3] = (uint32_t)(wT + 1);
-    J[kJobWords] = 0; J[kJobWords + 1] = (uint32_t)iNU; J[kJobWords + 3] = (uint32_t)(wT + 2);
-    if ((rc = sh_pow(c, sh_shape(true, 0), J, V, SC, W, Gt, Gt))) return rc;
+    J[0].base = (uint32_t)(N + 1); J[0].exp[0] = (uint32_t)iQm1; J[0].out[0] = (uint32_t)(wT + 1);
+    J[1].base = 0; J[1].exp[0] = (uint32_t)iNU; J[1].out[0] = (uint32_t)(wT + 2);
+    if ((rc = launch_pow_jobs(c, W_SH_JOBS, pow_var(), J, V, SC, W, Gt, Gt))) return rc;
   }
   if ((rc = sh_mul(c, W + wT * kW, 1, W + (wT + 1) * kW, 1, 1, W))) return rc;                 // cbar
   if ((rc = sh_mul(c, V + (vC + N) * kW, 1, W + (wT + 2) * kW, 1, 1, W + kW))) return rc;      // chat
@@ -646,16 +624,16 @@ static int sh_verify_locked(eg_ctx* c, const uint8_t* CN, size_t N, size_t w, co
   {
     auto JA = new_jobs(3 + w), JB = new_jobs(w);
     for (size_t k = 0; k < 3 + w; ++k) {
-      uint32_t* a = &JA[k * kJobWords];
+      PowJob& a = JA[k];
       const size_t e = k < 3 ? k : 3 + 2 * (k - 3);
-      a[0] = (uint32_t)e; a[1] = (uint32_t)iNC; a[3] = (uint32_t)e; a[5] = (uint32_t)(k < 3 ? iS + k : iNS4 + (k - 3));
+      a.base = (uint32_t)e; a.exp[0] = (uint32_t)iNC; a.out[0] = (uint32_t)e; a.fb[0][0] = (uint32_t)(k < 3 ? iS + k : iNS4 + (k - 3));
     }
     for (size_t j = 0; j < w; ++j) {
-      uint32_t* b = &JB[j * kJobWords];
-      b[0] = (uint32_t)(4 + 2 * j); b[1] = (uint32_t)iNC; b[3] = b[0]; b[5] = (uint32_t)(iNS4 + j);
+      PowJob& b = JB[j];
+      b.base = (uint32_t)(4 + 2 * j); b.exp[0] = (uint32_t)iNC; b.out[0] = b.base; b.fb[0][0] = (uint32_t)(iNS4 + j);
     }
-    if ((rc = sh_pow(c, sh_shape(true, 1), JA, W, SC, X, Gt, Gt))) return rc;
-    if ((rc = sh_pow(c, sh_shape(true, 1), JB, W, SC, X, Kt, Kt))) return rc;
+    if ((rc = launch_pow_jobs(c, W_SH_JOBS, pow_var(1, 32, 1), JA, W, SC, X, Gt, Gt))) return rc;
+    if ((rc = launch_pow_jobs(c, W_SH_JOBS, pow_var(1, 32, 1), JB, W, SC, X, Kt, Kt))) return rc;
   }
   // ... and for t3' and t4' times the products over N with the exponents s'
   if ((rc = sh_pp(c, G + 512, N, 1, sc(iSP), 1, N, X + xP * kW))) return rc;
@@ -667,13 +645,13 @@ static int sh_verify_locked(eg_ctx* c, const uint8_t* CN, size_t N, size_t w, co
   {
     auto JA = new_jobs(N), JB = new_jobs(N);
     for (size_t i = 0; i < N; ++i) {
-      uint32_t* a = &JA[i * kJobWords];
-      a[0] = (uint32_t)(vC + 1 + i); a[1] = (uint32_t)iNC; a[3] = (uint32_t)(xH + 2 * i); a[5] = (uint32_t)(iSH + i);
-      uint32_t* b = &JB[i * kJobWords];
-      b[0] = (uint32_t)(vC + i); b[1] = (uint32_t)(iSP + i); b[3] = (uint32_t)(xH + 2 * i + 1);
+      PowJob& a = JA[i];
+      a.base = (uint32_t)(vC + 1 + i); a.exp[0] = (uint32_t)iNC; a.out[0] = (uint32_t)(xH + 2 * i); a.fb[0][0] = (uint32_t)(iSH + i);
+      PowJob& b = JB[i];
+      b.base = (uint32_t)(vC + i); b.exp[0] = (uint32_t)(iSP + i); b.out[0] = (uint32_t)(xH + 2 * i + 1);
     }
-    if ((rc = sh_pow(c, sh_shape(true, 1), JA, V, SC, X, Gt, Gt))) return rc;
-    if ((rc = sh_pow(c, sh_shape(true, 0), JB, V, SC, X, Gt, Gt))) return rc;
+    if ((rc = launch_pow_jobs(c, W_SH_JOBS, pow_var(1, 32, 1), JA, V, SC, X, Gt, Gt))) return rc;
+    if ((rc = launch_pow_jobs(c, W_SH_JOBS, pow_var(), JB, V, SC, X, Gt, Gt))) return rc;
   }
   LAUNCH_F(c, k_mul, dim3(grid_for(N)), c->d, X + xH * kW, 2u, X + (xH + 1) * kW, 2u, (uint32_t)N, Y, 1u);
   HIPCHK(hipGetLastError());

@@ -7,6 +7,7 @@
 // a disabled lane.
 #pragma once
 #include "eg_bignum.hpp"
+#include "eg_powjob.hpp"
 #include "eg_sha256.hpp"
 
 namespace eg {
@@ -25,7 +26,6 @@ constexpr int kBlock = 256;
 #define EG_MIN_WAVES 3  // k_pow: 3 waves/SIMD (<= 168 VGPRs; a few squaring-loop spills, measured +1.3..1.6%)
 #endif
 constexpr int kGroupsPerBlock = kBlock / kT;
-constexpr uint32_t kNone = 0xFFFFFFFFu;
 
 struct FbTab {
   const uint32_t* data;  // (nwin << wbits) device elements, entry (k, d) = base^(d * 2^(wbits*k))
@@ -389,41 +389,9 @@ __global__ void __launch_bounds__(kBlock) k_mul(const MontConsts* __restrict__ C
 }
 
 // ---------------------------------------------------------------------------------
-// Exponentiation jobs.
-//   job record (kJobWords u32): base, e0, e1, out0, out1, f00, f01, f10, f11
-//   base    : element index of the variable base (kNone = no variable part)
-//   e0/e1   : scalar indices (32-B BE) of the variable-base exponents
-//   out0/1  : output element indices
-//   fXY     : scalar index of fixed-base term Y of output X
-// Launch-uniform shape: nout (1|2), nfb0/nfb1 (0..2), tab[X][Y] in {0,1} = which FbTab.
-// Variable part: fixed 4-bit window, table base^0..base^15 in per-group scratch.
+// Exponentiation jobs: the job record (PowJob, kJobWords u32 read by word offset) and the
+// launch-uniform PowShape are eg_powjob.hpp's.
 // ---------------------------------------------------------------------------------
-constexpr int kJobWords = 9;
-
-struct PowShape {
-  uint32_t has_base, nout, nfb[2], tab[2][2];
-  uint32_t exp_bytes;  // variable-base exponent length (32, or 512 for inverses)
-  uint32_t comb;       // 1: Lim-Lee comb (h = 5) shared by the job's exponents (32-byte only)
-  uint32_t gather;     // comb jobs whose base is a PRODUCT of `gather` earlier comb bases (the contest
-                       // aggregates A = prod alpha, B = prod beta): y_k = prod of their y_k (ygat,
-                       // job J[2] onwards) instead of 208 squarings; 0 = none
-  uint32_t resid;      // comb jobs (not gather): also write the residue-test pair of the base B,
-                       // z = B^(2^256) (the squaring chain run to the end) and w = B^c, c = 2^256 - q, to
-                       // rout[2 gid], rout[2 gid + 1]; B^q == 1 iff z == w and B != 0 (k_resid_check)
-  uint32_t shared_comb;  // comb jobs whose 32-entry subset table is PowPart::ctab (one table for every
-                         // job, e.g. the trustee's g^u): no per-job precompute
-  uint32_t blocks;     // Lim-Lee column blocks v of a plain comb (0/1: one block of cw columns, one
-                       // 2^h-entry table; 2 or 3: blocks of ceil(cw / v) columns, tables of
-                       // B^(2^(cw r + bw t)), v * 2^h entries).  v > 1 pays when the squaring chain
-                       // runs to 2^256 anyway (resid)
-  uint32_t rows;       // Lim-Lee rows h of a plain comb (0: kCombH = 5 rows of 52 bits, 32-entry
-                       // tables; 4: rows of 64 bits, 16-entry tables -- the constant-time trustee
-                       // pair, whose masked scans read every entry of a table, and the EG_SEL_COMB=43
-                       // selection jobs, 4 rows x 3 blocks)
-  uint32_t fb_small[2][2];  // fixed-base term [o][t] whose scalar is < 2^wbits (the vote m of
-                            // beta = K^R g^m): only radix window 0 is applied (host schedule only)
-};
-
 // Constant-time table read for secret digits (k_pow<F, CT = true>, the trustee's shares):
 // every entry of the table is read and the wanted one kept with a mask, so the addresses a
 // job touches do not depend on the digit d.  Each lane selects its own 20-word block.
@@ -482,7 +450,7 @@ __device__ __forceinline__ uint32_t be_digit(const uint8_t* __restrict__ e, int 
 // the host compiles every launch shape into a list of op words (pow_schedule in eg_capi.hip),
 // the same list for every job of the launch, and k_pow interprets it.  The op word is read
 // with a scalar load and every branch is wave-uniform; only the operands differ per job
-// (the base J[0], exponents J[1..2], fixed-base scalars J[5..8] and outputs J[3..4]).
+// (the PowJob fields: base, exp, fb and out).
 // Keeping the control state to one program counter (instead of a phase state machine)
 // leaves the multiply bodies with fewer live registers and no per-multiply bookkeeping.
 //   op = kind | arg << kOpShift
@@ -491,22 +459,22 @@ enum PowOp : uint32_t {
   OP_SQR,         // x <- x^2
   OP_MUL_BASE,    // x <- x * B
   OP_MUL_TBL,     // x <- x * tbl[arg]
-  OP_MUL_WIN,     // x <- x * tbl[nibble w of exponent J[1 + o]], arg = w | o << 12 (4-bit window, MSB first)
+  OP_MUL_WIN,     // x <- x * tbl[nibble w of exponent J[kJobExp + o]], arg = w | o << 12 (4-bit window, MSB first)
   OP_MUL_COMB,    // x <- x * tbl[dig[arg]]                      (Lim-Lee column arg)
-  OP_MUL_GATHER,  // x <- x * y_{k}(job J[2] + i), arg = i << 2 | (k - 1)
-  OP_MUL_FB,      // x <- x * T[kf][digit kf of scalar J[5 + 2o + t]], arg = fb_arg(o, t, tab, kf)
+  OP_MUL_GATHER,  // x <- x * y_{k}(job J[kJobGather] + i), arg = i << 2 | (k - 1)
+  OP_MUL_FB,      // x <- x * T[kf][digit kf of scalar J[kJobFb + 2o + t]], arg = fb_arg(o, t, tab, kf)
   OP_LOAD_ONE,    // x <- R mod p
   OP_LOAD_BASE,   // x <- B
   OP_LOAD_TBL,    // x <- tbl[arg]
-  OP_LOAD_WIN,    // x <- tbl[nibble 0 of exponent J[1 + arg]]
+  OP_LOAD_WIN,    // x <- tbl[nibble 0 of exponent J[kJobExp + arg]]
   OP_LOAD_COMB,   // x <- tbl[dig[arg]]
-  OP_LOAD_GATHER, // x <- y_{arg + 1}(job J[2])
+  OP_LOAD_GATHER, // x <- y_{arg + 1}(job J[kJobGather])
   OP_LOAD_FB,     // x <- T[kf][digit], arg as OP_MUL_FB
   OP_STORE_TBL,   // tbl[arg] <- x
   OP_STORE_Y,     // yout[job][arg] <- x                         (if the part has yout)
   OP_STORE_R,     // rout[job][arg] <- x                         (residue pair)
-  OP_STORE_OUT,   // out[J[3 + arg]] <- x
-  OP_EXP,         // comb shapes: spread the column digits of exponent J[1 + arg] to dig[]
+  OP_STORE_OUT,   // out[J[kJobOut + arg]] <- x
+  OP_EXP,         // comb shapes: spread the column digits of exponent J[kJobExp + arg] to dig[]
 };
 constexpr uint32_t kOpShift = 5;
 constexpr uint32_t kOpMulLast = OP_MUL_FB;
@@ -576,7 +544,7 @@ __global__ void __launch_bounds__(kBlock, EG_MIN_WAVES) k_pow(const MontConsts* 
   const uint32_t* J = P.jobs + (size_t)(live ? gid : njobs - 1) * kJobWords;
   // shared comb table (read-only: the schedule has no precompute) or the job's scratch table
   uint32_t* tbl = (S.comb && S.shared_comb) ? const_cast<uint32_t*>(P.ctab) : P.scratch + (size_t)gid * tsize * kW;
-  const uint32_t* B = (S.has_base && !S.shared_comb) ? elems + (size_t)J[0] * kW : nullptr;
+  const uint32_t* B = (S.has_base && !S.shared_comb) ? elems + (size_t)J[kJobBase] * kW : nullptr;
 
   // Outer loop: one Montgomery multiply (or square) per trip, at a single inlined site; the
   // inner loop runs the program's loads, stores and digit spreads up to the next multiply.
@@ -591,7 +559,7 @@ __global__ void __launch_bounds__(kBlock, EG_MIN_WAVES) k_pow(const MontConsts* 
       if (kind == OP_LOAD_FB) {
         const FbTab& T = (arg >> 10) ? fb1 : fb0;
         const uint32_t kf = arg & 255u;
-        const uint32_t d = be_digit(scalars + (size_t)J[5 + 2 * ((arg >> 9) & 1u) + ((arg >> 8) & 1u)] * 32, 32,
+        const uint32_t d = be_digit(scalars + (size_t)J[kJobFb + 2 * ((arg >> 9) & 1u) + ((arg >> 8) & 1u)] * 32, 32,
                                     kf * T.wbits, T.wbits);
         if constexpr (CT) {
           // secret scalar (encryption nonces, the vote): masked scan of the window's whole
@@ -609,7 +577,7 @@ __global__ void __launch_bounds__(kBlock, EG_MIN_WAVES) k_pow(const MontConsts* 
           case OP_LOAD_BASE: load_elem(x, B); break;
           case OP_LOAD_TBL: load_elem(x, tbl + (size_t)arg * kW); break;
           case OP_LOAD_WIN: {
-            const uint32_t d = scalars[(size_t)J[1 + arg] * S.exp_bytes] >> 4;
+            const uint32_t d = scalars[(size_t)J[kJobExp + arg] * S.exp_bytes] >> 4;
             if constexpr (CT) {  // secret exponent (eg_ctx_set_ct_pow): masked scan of the 16-entry table
               ct_select_to_lds(slot, tbl, 4, d);
               wave_sync();
@@ -630,7 +598,7 @@ __global__ void __launch_bounds__(kBlock, EG_MIN_WAVES) k_pow(const MontConsts* 
               load_elem(x, tbl + (size_t)dig[arg] * kW);
             }
             break;
-          case OP_LOAD_GATHER: load_elem(x, P.ygat + ((size_t)J[2] * (kCombH - 1) + arg) * kW); break;
+          case OP_LOAD_GATHER: load_elem(x, P.ygat + ((size_t)J[kJobGather] * (kCombH - 1) + arg) * kW); break;
           case OP_STORE_TBL: store_elem(tbl + (size_t)arg * kW, x); break;
           case OP_STORE_Y:
             if (P.yout != nullptr && live) store_elem(P.yout + ((size_t)gid * (kCombH - 1) + arg) * kW, x);
@@ -639,14 +607,14 @@ __global__ void __launch_bounds__(kBlock, EG_MIN_WAVES) k_pow(const MontConsts* 
             if (live) store_elem(P.rout + ((size_t)gid * 2 + arg) * kW, x);
             break;
           case OP_STORE_OUT:
-            if (live) store_elem(out + (size_t)J[3 + arg] * kW, x);
+            if (live) store_elem(out + (size_t)J[kJobOut + arg] * kW, x);
             break;
           case OP_EXP:
             if (S.comb) {
-              // column digits of exponent J[1 + arg]: bit j of each of the h rows (cw bits each);
+              // column digits of exponent J[kJobExp + arg]: bit j of each of the h rows (cw bits each);
               // with v column blocks of bw = ceil(cw / v) columns, column j indexes table j / bw
               // (entry (j / bw) * 2^h + digit)
-              const uint8_t* e = scalars + (size_t)J[1 + arg] * 32;
+              const uint8_t* e = scalars + (size_t)J[kJobExp + arg] * 32;
               const int cw = (int)comb_width(S.rows);
               const int bw = (int)comb_block_width(S.rows, S.blocks);
               wave_sync();
@@ -678,15 +646,15 @@ __global__ void __launch_bounds__(kBlock, EG_MIN_WAVES) k_pow(const MontConsts* 
     else if (kind == OP_MUL_TBL) ysrc = tbl + (size_t)arg * kW;
     else if (kind == OP_MUL_WIN) {  // arg = w | o << 12
       const uint32_t w = arg & 4095u;
-      const uint32_t byte = scalars[(size_t)J[1 + (arg >> 12)] * S.exp_bytes + (w >> 1)];
+      const uint32_t byte = scalars[(size_t)J[kJobExp + (arg >> 12)] * S.exp_bytes + (w >> 1)];
       ysrc = tbl + (size_t)((w & 1) ? (byte & 15u) : (byte >> 4)) * kW;
       fb_d = (w & 1) ? (byte & 15u) : (byte >> 4);  // CT: the window digit the masked scan selects
     } else if (kind == OP_MUL_COMB) ysrc = tbl + (size_t)dig[arg] * kW;
-    else if (kind == OP_MUL_GATHER) ysrc = P.ygat + ((size_t)(J[2] + (arg >> 2)) * (kCombH - 1) + (arg & 3u)) * kW;
+    else if (kind == OP_MUL_GATHER) ysrc = P.ygat + ((size_t)(J[kJobGather] + (arg >> 2)) * (kCombH - 1) + (arg & 3u)) * kW;
     else if (kind == OP_MUL_FB) {
       const FbTab& T = (arg >> 10) ? fb1 : fb0;
       const uint32_t kf = arg & 255u;
-      const uint32_t d = be_digit(scalars + (size_t)J[5 + 2 * ((arg >> 9) & 1u) + ((arg >> 8) & 1u)] * 32, 32,
+      const uint32_t d = be_digit(scalars + (size_t)J[kJobFb + 2 * ((arg >> 9) & 1u) + ((arg >> 8) & 1u)] * 32, 32,
                                   kf * T.wbits, T.wbits);
       fb_col = T.data + (size_t)(kf << T.wbits) * kW;
       fb_h = T.wbits;

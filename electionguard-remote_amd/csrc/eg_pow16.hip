@@ -89,11 +89,7 @@ int pow16_powp(const Pow16Consts* C, bool friendly, bool ct, hipStream_t s, cons
                uint32_t* outs, uint32_t* scratch, std::string* err) {
   if (!n) return 0;
   const unsigned grid = (unsigned)((n + kGroupsPerBlock - 1) / kGroupsPerBlock);
-  PowShape S{};
-  S.has_base = 1;
-  S.nout = 1;
-  S.exp_bytes = 32;
-  PowPart P0{S, sched, jobs, (uint32_t)n, grid, scratch, nullptr, nullptr, nullptr, nullptr};
+  PowPart P0{pow_var(), sched, jobs, (uint32_t)n, grid, scratch, nullptr, nullptr, nullptr, nullptr};
   PowPart none{};
   const FbTab nofb{nullptr, 0, 0};
   if (friendly) {

@@ -380,6 +380,59 @@ def test_a_run_that_crosses_the_chunk(group, ceremonies):
     assert not ok[ch, 1] and ok.sum() == n * k - 1
 
 
+def test_check_on_the_guardians_tables_against_the_reference(group, ceremonies):
+    """k = 2 and n = 8193: at 8192 texts and more the check reads Z_i^c from the guardians' cached
+    radix tables, with guardian-major jobs, here in one full chunk of 8192 texts and a second of
+    one.  The rows tile 24 texts of one CPython run, five edge texts (A = 1, g, p - 1, 0, p + 5) and
+    19 encryptions; a c_i, a v_i and a commitment of encryptions are altered in both chunks and on
+    both guardians, and every ok flag and v sum comes from the reference."""
+    from electionguard import decrypt2 as D
+    cer, xs, k, per = ceremonies[(3, 2)], [1, 3], 2, 24
+    p, q, g = group.p, group.q, group.g
+    n = D.chunk_texts(k) + 1
+    assert n == 8193
+    rng = random.Random(53)
+    texts = edge_texts(group, rng, 5)
+    for t in range(per - 5):
+        r = rng.randrange(1, q)
+        texts.append((pow(g, r, p), pow(cer.K, r, p) * pow(g, t, p) % p))
+    run = R.run(cer, QBAR, xs, texts, nonce_rows(group, rng, k, per))
+    assert run.ok[5:] == [[True] * k] * (per - 5) and run.ok[:5] != [[True] * k] * 5
+    a = arrays(run)
+    idx = np.arange(n) % per
+    T, shares, comm, ci, vi = (np.ascontiguousarray(x[idx]) for x in (a.T, a.shares, a.comm, a.ci, a.vi))
+    # (row, guardian, what): rows 0..8191 are the first chunk, row 8192 the second
+    tamperings = [(6, 0, "ci"), (101, 1, "ci=q"), (4097, 1, "vi"), (8191, 0, "ai"), (8192, 0, "vi"), (8192, 1, "bi")]
+    assert all(r % per >= 5 for r, _, _ in tamperings)
+    want_ok = np.array(run.ok, bool)[idx]
+    want_v = Q(run.v)[idx]
+    for row in sorted({r for r, _, _ in tamperings}):
+        t = row % per
+        sh, cm = list(run.shares[t]), [list(x) for x in run.comm[t]]
+        cr, vr = list(run.ci[t]), list(run.vi[t])
+        for r, i, what in tamperings:
+            if r != row:
+                continue
+            if what == "ci":
+                cr[i] = (cr[i] + 1) % q
+            elif what == "ci=q":
+                cr[i] = q
+            elif what == "vi":
+                vr[i] = (vr[i] + 1) % q
+            else:
+                cm[i]["ab".index(what[0])] = cm[i]["ab".index(what[0])] * g % p
+        ok1, v1 = R.check(p, q, g, run.Z, [run.texts[t]], [sh], [cm], [cr], [vr])
+        assert ok1[0] == [not any(r == row and j == i for r, j, _ in tamperings) for i in range(k)], row
+        want_ok[row], want_v[row] = ok1[0], be(v1[0], 32)
+        comm[row], ci[row], vi[row] = np.stack([np.stack([be(x), be(y)]) for x, y in cm]), Q(cr), Q(vr)
+    assert (~want_ok).sum() == (~np.array(run.ok, bool)[idx]).sum() + len(tamperings)
+    for up in (lambda x: x, group.to_device):
+        ok, v = D.check(group, run.Z, up(T), up(shares), up(comm), up(ci), up(vi))
+        ok = np.asarray(ok.download() if hasattr(ok, "download") else ok).astype(bool).reshape(n, k)
+        assert np.array_equal(ok, want_ok), np.argwhere(ok != want_ok)[:8].tolist()
+        assert eq(v, want_v)
+
+
 def test_commit_and_respond_cross_their_chunk(group):
     """One text more than the trustee calls' chunk: the bytes of the two halves called apart."""
     from electionguard import decrypt2 as D
