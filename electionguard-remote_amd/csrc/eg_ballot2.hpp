@@ -13,6 +13,7 @@
 // ballot's ragged array, in units the caller scales (mul) and shifts (shift).
 #pragma once
 #include "eg_range.hpp"
+#include "eg_u256.hpp"
 
 namespace eg {
 
@@ -57,10 +58,7 @@ __global__ void __launch_bounds__(kBlock) k_b2_ctscal(const uint8_t* __restrict_
   const uint64_t b = i / NS;
   const uint32_t s = (uint32_t)(i % NS);
   st256(sc + i * 64, ld256(sel_nonces + (b * SN + sn_row[s]) * 32));
-  U256 m;
-  for (int w = 0; w < 8; ++w) m.w[w] = 0;
-  m.w[0] = votes[i];
-  st256(sc + i * 64 + 32, m);
+  st256(sc + i * 64 + 32, u256_small(votes[i]));
 }
 
 // Per (ballot, contest) j = b * nc + k: rsum[j] = sum of its selections' R mod q, and value[j],
@@ -85,8 +83,7 @@ __global__ void __launch_bounds__(kBlock) k_b2_sums(const uint8_t* __restrict__ 
   const U256 q = ld256(q_be);
   const uint8_t* v = votes + b * NS + first[k];
   const uint8_t* R = sel_nonces + (b * SN + sn_off[k]) * 32;
-  U256 r;
-  for (int w = 0; w < 8; ++w) r.w[w] = 0;
+  U256 r = u256_zero();
   uint32_t M = 0;
   for (uint32_t s = 0; s < n; ++s) {
     r = addmod256(r, ld256(R + (uint64_t)s * rows * 32), q);

@@ -40,6 +40,7 @@
 #include "../../include/eg_hip_decrypt2.h"
 #include "../../include/eg_hip_shuffle.h"
 #include "eg_kernels.hpp"
+#include "eg_proof_kernels.hpp"
 #include "eg_codes.hpp"
 #include "eg_hmac.hpp"
 #include "eg_range.hpp"

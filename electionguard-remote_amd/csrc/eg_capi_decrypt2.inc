@@ -88,7 +88,7 @@ extern "C" int eg_decrypt2_respond(eg_ctx* c, const uint8_t secret_be[32], const
     HIPCHK(hipMemcpyAsync(SC, secret_be, 32, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(SC + 32, nonces + i0 * 32, m * 32, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(SC + (1 + m) * 32, challenges + i0 * 32, m * 32, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_d2_reduce, dim3(cgrid(2 * m + 1)), dim3(kBlock), 0, c->stream, c->d_q, SC, (uint64_t)(2 * m + 1));
+    hipLaunchKernelGGL(k_reduce_q, dim3(cgrid(2 * m + 1)), dim3(kBlock), 0, c->stream, c->d_q, SC, (uint64_t)(2 * m + 1), SC);
     HIPCHK(hipGetLastError());
     if ((rc = ws_get(c, W_OK1, m * 64, (void**)&PR))) return rc;
     hipLaunchKernelGGL(k_response, dim3(cgrid(m)), dim3(256), 0, c->stream, c->d_q, SC + 32, SC + (1 + m) * 32, SC, 0u,

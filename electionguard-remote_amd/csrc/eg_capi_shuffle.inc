@@ -134,7 +134,7 @@ static int sh_mix(eg_ctx* c, bool host, const uint8_t* K_be, size_t N, size_t w,
     d_E = X;
     d_r = SC + cells * 32;
   }
-  hipLaunchKernelGGL(k_sh_reduce, dim3(cgrid(cells)), dim3(kBlock), 0, c->stream, c->d_q, d_r, (uint64_t)cells, SC);
+  hipLaunchKernelGGL(k_reduce_q, dim3(cgrid(cells)), dim3(kBlock), 0, c->stream, c->d_q, d_r, (uint64_t)cells, SC);
   HIPCHK(hipGetLastError());
   if ((rc = ws_get(c, W_SH_E, items * E, (void**)&EL))) return rc;
   if ((rc = launch_import(c, d_E, items, EL, nullptr))) return rc;
@@ -320,7 +320,7 @@ static int sh_scan(eg_ctx* c, uint8_t* A, uint8_t* B, size_t n, uint8_t* T) {
 }
 
 static int sh_reduce(eg_ctx* c, const uint8_t* in, size_t n, uint8_t* out) {
-  hipLaunchKernelGGL(k_sh_reduce, dim3(cgrid(n)), dim3(kBlock), 0, c->stream, c->d_q, in, (uint64_t)n, out);
+  hipLaunchKernelGGL(k_reduce_q, dim3(cgrid(n)), dim3(kBlock), 0, c->stream, c->d_q, in, (uint64_t)n, out);
   HIPCHK(hipGetLastError());
   return EG_OK;
 }

@@ -1,6 +1,7 @@
 // eg_codes2.hpp — ballot nonces from one per-ballot seed and the opening of challenged ballots for
 // the placeholder-free ballot (include/eg_hip_codes2.h).  The hashes are
-// eg_codes.hpp's hash_elems; the ragged row layouts are include/eg_hip_ballot2.h's.
+// eg_hash_elems.hpp's hash_elems, closed as eg_codes.hpp's are; the ragged row layouts are
+// include/eg_hip_ballot2.h's.
 //
 //   sel_nonces[b, r]     = H(xi_b, 5, r)      0 <= r < SN
 //   contest_nonces[b, r] = H(xi_b, 6, r)      0 <= r < CN
@@ -8,10 +9,11 @@
 //   open: ok = (alpha == g^R) and (beta == K^R g^m for one m in 0..olimit[k]); votes = m, else 0
 //
 // The hash kernels follow DESIGN §11: one thread per hash, 256-thread workgroups, 64-bit indices,
-// no barrier, the SHA block buffer in LDS at kCodeBufStride.  The match kernel is eg_kernels.hpp's
+// no barrier, the SHA block buffer in LDS at kHashBufStride.  The match kernel is eg_kernels.hpp's
 // shape: one selection per group of kT lanes, tail groups recompute a clamped selection.
 #pragma once
-#include "eg_codes.hpp"
+#include "eg_hash_elems.hpp"
+#include "eg_kernels.hpp"
 
 namespace eg {
 
@@ -22,7 +24,7 @@ __global__ void __launch_bounds__(256) k_b2_derive_nonces(const uint8_t* __restr
                                                           uint32_t SN, uint32_t CN, uint8_t* __restrict__ sel_nonces,
                                                           uint8_t* __restrict__ contest_nonces,
                                                           uint32_t hash_minimal) {
-  __shared__ uint32_t s_buf[256 * kCodeBufStride];
+  __shared__ uint32_t s_buf[256 * kHashBufStride];
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   const uint64_t nsn = nb * SN;
   if (i >= nsn + nb * CN) return;
@@ -31,17 +33,11 @@ __global__ void __launch_bounds__(256) k_b2_derive_nonces(const uint8_t* __restr
   const uint64_t per = is_sel ? (uint64_t)SN : (uint64_t)CN;
   const uint64_t b = j / per;
   const uint32_t r = (uint32_t)(j - b * per);
-  const bool mn = hash_minimal != 0;
-  Sha256 H;
-  H.init(s_buf + threadIdx.x * kCodeBufStride);
-  H.put('|');
-  H.put_hex(ballot_nonces + b * 32, 32, mn);
-  H.put('|');
-  put_hex_small(H, is_sel ? 5u : 6u, mn);
-  H.put('|');
-  put_hex_small(H, r, mn);
-  H.put('|');
-  st256((is_sel ? sel_nonces : contest_nonces) + j * 32, finish_mod_q(H, q_be));
+  HashElems H(s_buf, hash_minimal);
+  H.q(ballot_nonces + b * 32);
+  H.small(is_sel ? 5u : 6u);
+  H.small(r);
+  st256((is_sel ? sel_nonces : contest_nonces) + j * 32, H.mod_q_top(ld256(q_be)));
 }
 
 // One thread per selection i = b * NS + s: only its R, row sn_row[s] of the ballot's selection
@@ -50,21 +46,15 @@ __global__ void __launch_bounds__(256) k_b2_derive_r(const uint8_t* __restrict__
                                                      const uint8_t* __restrict__ ballot_nonces,
                                                      const uint32_t* __restrict__ sn_row, uint32_t NS, uint64_t n,
                                                      uint8_t* __restrict__ R, uint32_t hash_minimal) {
-  __shared__ uint32_t s_buf[256 * kCodeBufStride];
+  __shared__ uint32_t s_buf[256 * kHashBufStride];
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const uint64_t b = i / NS;
-  const bool mn = hash_minimal != 0;
-  Sha256 H;
-  H.init(s_buf + threadIdx.x * kCodeBufStride);
-  H.put('|');
-  H.put_hex(ballot_nonces + b * 32, 32, mn);
-  H.put('|');
-  put_hex_small(H, 5u, mn);
-  H.put('|');
-  put_hex_small(H, sn_row[i - b * NS], mn);
-  H.put('|');
-  st256(R + i * 32, finish_mod_q(H, q_be));
+  HashElems H(s_buf, hash_minimal);
+  H.q(ballot_nonces + b * 32);
+  H.small(5u);
+  H.small(sn_row[i - b * NS]);
+  st256(R + i * 32, H.mod_q_top(ld256(q_be)));
 }
 
 // This lane's limbs of the 512 big-endian bytes at be (any value below 2^4096), through the slot.

@@ -1,31 +1,15 @@
 // eg_decrypt2.hpp — the scalar and compare kernels of the threshold decryption with one combined
 // proof per text (include/eg_hip_decrypt2.h).  DESIGN §11's conventions: one thread
 // per item, 256 threads per block, 64-bit indices, no barrier.  The exponentiations, products and
-// hashes of the family are k_pow, k_prod, k_pp_* and k_hash_check (eg_kernels.hpp, eg_prodpow.hpp).
+// hashes of the family are k_pow, k_prod, k_pp_* and k_hash_check (eg_kernels.hpp, eg_prodpow.hpp,
+// eg_proof_kernels.hpp); the reduction of the secret, the nonces and the challenges of
+// eg_decrypt2_respond mod q is eg_proof_kernels.hpp's k_reduce_q, in place.
 #pragma once
 
 #include "eg_kernels.hpp"
+#include "eg_u256.hpp"
 
 namespace eg {
-
-// x mod q for ANY 256-bit x and any q > 1, branch-free in x: the double-and-add ladder of
-// mulmod256 over x's bits with the addend 1 (the trustee's secret and nonces pass through here)
-__device__ __forceinline__ U256 d2_modq(const U256& x, const U256& q) {
-  U256 one;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) one.w[k] = 0;
-  one.w[0] = 1;
-  return mulmod256(x, one, q);
-}
-
-// io[i] = io[i] mod q  (the secret, the nonces and the challenges of eg_decrypt2_respond, in place)
-__global__ void __launch_bounds__(kBlock) k_d2_reduce(const uint8_t* __restrict__ q_be, uint8_t* __restrict__ io,
-                                                       uint64_t n) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const U256 q = ld256(q_be);
-  st256(io + i * 32, d2_modq(ld256(io + i * 32), q));
-}
 
 // ci[t, i] = c[t] * (w[i] mod q) mod q  (item j = t * k + i; c < q comes from the device hash)
 __global__ void __launch_bounds__(kBlock) k_d2_ci(const uint8_t* __restrict__ q_be, const uint8_t* __restrict__ c_be,
@@ -34,7 +18,7 @@ __global__ void __launch_bounds__(kBlock) k_d2_ci(const uint8_t* __restrict__ q_
   const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= items) return;
   const U256 q = ld256(q_be);
-  const U256 w = d2_modq(ld256(w_be + (j % k) * 32), q);
+  const U256 w = mod256_any(ld256(w_be + (j % k) * 32), q);
   st256(ci + j * 32, mulmod256(ld256(c_be + (j / k) * 32), w, q));
 }
 
@@ -56,14 +40,8 @@ __global__ void __launch_bounds__(kBlock) k_d2_match(const uint8_t* __restrict__
                                                       uint8_t* __restrict__ ok) {
   const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
-  const uint4* x = reinterpret_cast<const uint4*>(got + j * 1024);
-  const uint4* y = reinterpret_cast<const uint4*>(given + j * 1024);
-  uint32_t diff = 0;
-#pragma unroll 4
-  for (int t = 0; t < 64; ++t) {
-    const uint4 u = x[t], v = y[t];
-    diff |= (u.x ^ v.x) | (u.y ^ v.y) | (u.z ^ v.z) | (u.w ^ v.w);
-  }
+  const uint32_t diff = quads_diff(reinterpret_cast<const uint4*>(got + j * 1024),
+                                   reinterpret_cast<const uint4*>(given + j * 1024), 64);
   ok[j] = (diff == 0 && pre[j] != 0) ? 1 : 0;
 }
 
@@ -73,10 +51,8 @@ __global__ void __launch_bounds__(kBlock) k_d2_vsum(const uint8_t* __restrict__ 
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n) return;
   const U256 q = ld256(q_be);
-  U256 r;
-#pragma unroll
-  for (int w = 0; w < 8; ++w) r.w[w] = 0;
-  for (uint32_t i = 0; i < k; ++i) r = addmod256(r, d2_modq(ld256(vi + (t * k + i) * 32), q), q);
+  U256 r = u256_zero();
+  for (uint32_t i = 0; i < k; ++i) r = addmod256(r, mod256_any(ld256(vi + (t * k + i) * 32), q), q);
   st256(v + t * 32, r);
 }
 

@@ -1,7 +1,7 @@
 // eg_hmac.hpp — HMAC-SHA256 on the device SHA-256, and the contest-data kernels
 // (include/eg_hip_contestdata.h): a contest's write-ins and overvote status under HashedElGamal.
 //
-//   r[b,k]  = H(xi_b, 3, k)                                  hash_elems, as eg_codes.hpp
+//   r[b,k]  = H(xi_b, 3, k)                                  hash_elems (eg_hash_elems.hpp)
 //   kk      = SHA256(c0 || kappa)                            1024 raw bytes; c0 = g^r, kappa = K^r
 //   block j = HMAC(kk, 0x01 || "contest" || label || be32(j))    label = ballot_id[b] || be32(k)
 //   mk      = HMAC(kk, 0x02 || "contest" || label)
@@ -13,11 +13,11 @@
 // stream block costs two compressions instead of four.
 //
 // As in eg_codes.hpp: one thread per item, 256 threads per block, 64-bit indices, no barrier, the
-// block buffer in LDS at the 17-word stride.  A thread owns ONE block buffer, so the stream and
+// block buffer in LDS at kHashBufStride.  A thread owns ONE block buffer, so the stream and
 // the MAC are two passes: seal writes c1 and then hashes it back from where it lies (a thread
 // reads its own stores), open hashes c1 first and then decrypts it.
 #pragma once
-#include "eg_codes.hpp"
+#include "eg_hash_elems.hpp"
 
 namespace eg {
 
@@ -166,21 +166,15 @@ __device__ __forceinline__ bool cd_word_rows(const void* a, const void* b, uint3
 __global__ void __launch_bounds__(256) k_cd_nonces(const uint8_t* __restrict__ q_be,
                                                    const uint8_t* __restrict__ ballot_nonces, uint64_t n, uint32_t nc,
                                                    uint8_t* __restrict__ out, uint32_t hash_minimal) {
-  __shared__ uint32_t s_buf[256 * kCodeBufStride];
+  __shared__ uint32_t s_buf[256 * kHashBufStride];
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const uint64_t b = i / nc;
-  const bool mn = hash_minimal != 0;
-  Sha256 H;
-  H.init(s_buf + threadIdx.x * kCodeBufStride);
-  H.put('|');
-  H.put_hex(ballot_nonces + b * 32, 32, mn);
-  H.put('|');
-  put_hex_small(H, 3u, mn);
-  H.put('|');
-  put_hex_small(H, (uint32_t)(i - b * nc), mn);
-  H.put('|');
-  st256(out + i * 32, finish_mod_q(H, q_be));
+  HashElems H(s_buf, hash_minimal);
+  H.q(ballot_nonces + b * 32);
+  H.small(3u);
+  H.small((uint32_t)(i - b * nc));
+  st256(out + i * 32, H.mod_q_top(ld256(q_be)));
 }
 
 // One thread per item: c1 (n, nbytes) = data XOR stream, c2 (n, 32) = HMAC(mk, c0 || c1).
@@ -188,13 +182,13 @@ __global__ void __launch_bounds__(256) k_cd_seal(const uint8_t* __restrict__ bal
                                                  const uint8_t* __restrict__ c0, const uint8_t* __restrict__ kappa,
                                                  const uint8_t* __restrict__ data, uint64_t n, uint32_t nc,
                                                  uint32_t nbytes, uint8_t* c1, uint8_t* __restrict__ c2) {
-  __shared__ uint32_t s_buf[256 * kCodeBufStride];
+  __shared__ uint32_t s_buf[256 * kHashBufStride];
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const uint64_t b = i / nc;
   const bool words = cd_word_rows(data, c1, nbytes);
   Sha256 H;
-  H.init(s_buf + threadIdx.x * kCodeBufStride);
+  H.init(s_buf + threadIdx.x * kHashBufStride);
   CdKeys S;
   cd_keys(H, ballot_ids, b, (uint32_t)(i - b * nc), c0 + i * 512, kappa + i * 512, S);
   uint8_t* row = c1 + i * nbytes;
@@ -213,13 +207,13 @@ __global__ void __launch_bounds__(256) k_cd_open(const uint8_t* __restrict__ bal
                                                  const uint8_t* __restrict__ c1, const uint8_t* __restrict__ c2,
                                                  uint64_t n, uint32_t nc, uint32_t nbytes, uint8_t* __restrict__ data,
                                                  uint8_t* __restrict__ ok) {
-  __shared__ uint32_t s_buf[256 * kCodeBufStride];
+  __shared__ uint32_t s_buf[256 * kHashBufStride];
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const uint64_t b = i / nc;
   const bool words = cd_word_rows(data, c1, nbytes);
   Sha256 H;
-  H.init(s_buf + threadIdx.x * kCodeBufStride);
+  H.init(s_buf + threadIdx.x * kHashBufStride);
   CdKeys S;
   cd_keys(H, ballot_ids, b, (uint32_t)(i - b * nc), c0 + i * 512, kappa + i * 512, S);
   uint32_t mac[8];

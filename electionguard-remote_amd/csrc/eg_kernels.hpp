@@ -1,4 +1,8 @@
-// eg_kernels.hpp — HIP kernels for the batched ElectionGuard group path on gfx950.
+// eg_kernels.hpp — HIP kernels for the batched ElectionGuard group path on gfx950: the Montgomery
+// kernels (import / export, k_pow, products, fixed-base tables) and, at the end, two inline helpers
+// on the canonical byte rows that k_export writes (row512_or, quads_diff).  No kernel here touches
+// a 256-bit scalar or a hash, so this is all the 16-lane unit (eg_pow16.hip) compiles; the scalar
+// and hash kernels around k_pow are eg_proof_kernels.hpp, on eg_u256.hpp and eg_hash_elems.hpp.
 //
 // All kernels run one element per group of kT lanes (eg_bignum.hpp) with 256-thread
 // workgroups and keep every Montgomery multiply WAVE-UNIFORM: per-launch shape
@@ -8,7 +12,6 @@
 #pragma once
 #include "eg_bignum.hpp"
 #include "eg_powjob.hpp"
-#include "eg_sha256.hpp"
 
 namespace eg {
 
@@ -876,341 +879,36 @@ __global__ void __launch_bounds__(kLdsBlock, 1) k_fb_lds(const MontConsts* __res
 }
 
 // ---------------------------------------------------------------------------------
-// 256-bit scalar helpers (one thread per scalar).  Scalars are 32-B big-endian.
+// Canonical byte rows (k_export's 512 big-endian bytes per element, 16-byte aligned), one thread
+// per row: the scans and compares the families' verdict kernels share.
 // ---------------------------------------------------------------------------------
-struct U256 {
-  uint32_t w[8];  // little-endian words
-};
-__device__ __forceinline__ U256 ld256(const uint8_t* __restrict__ be) {
-  U256 r;
-  const uint32_t* s = reinterpret_cast<const uint32_t*>(be);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) r.w[i] = __builtin_bswap32(s[7 - i]);
-  return r;
-}
-__device__ __forceinline__ void st256(uint8_t* __restrict__ be, const U256& a) {
-  uint32_t* d = reinterpret_cast<uint32_t*>(be);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) d[7 - i] = __builtin_bswap32(a.w[i]);
-}
-// The mod-q helpers below are branch-free in their operands (trustee responses v = u - c s and
-// the encryption's R c_fake touch secrets): a < b is the borrow of a - b, selections are masks.
-__device__ __forceinline__ bool lt256(const U256& a, const U256& b) {
-  int64_t c = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    c += (int64_t)a.w[i] - (int64_t)b.w[i];
-    c >>= 32;
+// OR of the 128 words of a 512-byte row, the last word (the element's low four bytes, the lowest
+// in the word's top byte) entering as (w & keep) ^ flip.  Zero iff the row is
+//   0        with keep = ~0u, flip = 0
+//   0 or 1   with keep = ~0x01000000u, flip = 0
+//   1        with keep = ~0u, flip = 0x01000000u
+__device__ __forceinline__ uint32_t row512_or(const uint8_t* __restrict__ row, uint32_t keep, uint32_t flip) {
+  const uint4* r = reinterpret_cast<const uint4*>(row);
+  uint32_t any = 0;
+#pragma unroll 4
+  for (int t = 0; t < 31; ++t) {
+    const uint4 v = r[t];
+    any |= v.x | v.y | v.z | v.w;
   }
-  return c != 0;
+  const uint4 v = r[31];
+  return any | v.x | v.y | v.z | ((v.w & keep) ^ flip);
 }
-__device__ __forceinline__ U256 sel256(uint32_t mask, const U256& a, const U256& b) {  // mask ? a : b
-  U256 r;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) r.w[i] = (a.w[i] & mask) | (b.w[i] & ~mask);
-  return r;
-}
-__device__ __forceinline__ uint32_t add256(U256& a, const U256& b) {
-  uint64_t c = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    c += (uint64_t)a.w[i] + b.w[i];
-    a.w[i] = (uint32_t)c;
-    c >>= 32;
+
+// OR of the differences of two runs of n uint4: zero iff the runs are equal; every quad is read
+// whatever the earlier ones gave
+__device__ __forceinline__ uint32_t quads_diff(const uint4* __restrict__ x, const uint4* __restrict__ y, uint64_t n) {
+  uint32_t diff = 0;
+#pragma unroll 4
+  for (uint64_t t = 0; t < n; ++t) {
+    const uint4 u = x[t], v = y[t];
+    diff |= (u.x ^ v.x) | (u.y ^ v.y) | (u.z ^ v.z) | (u.w ^ v.w);
   }
-  return (uint32_t)c;
-}
-__device__ __forceinline__ uint32_t sub256(U256& a, const U256& b) {
-  int64_t c = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    c += (int64_t)a.w[i] - (int64_t)b.w[i];
-    a.w[i] = (uint32_t)c;
-    c >>= 32;
-  }
-  return (uint32_t)(c & 1);
-}
-// (a + b) mod q for a, b < q
-__device__ __forceinline__ U256 addmod256(U256 a, const U256& b, const U256& q) {
-  const uint32_t carry = add256(a, b);
-  U256 t = a;
-  const uint32_t borrow = sub256(t, q);
-  return sel256(0u - (carry | (borrow ^ 1u)), t, a);  // subtract q iff a + b >= q
-}
-// (L * a) mod q for a < q, L < 2^32  (schoolbook + repeated subtraction-free fold)
-__device__ __forceinline__ U256 mulsmall_mod(const U256& a, uint32_t L, const U256& q) {
-  // r = L*a as 288-bit, then reduce by long division on the top word
-  uint32_t r[9];
-  uint64_t c = 0;
-  for (int i = 0; i < 8; ++i) {
-    c += (uint64_t)a.w[i] * L;
-    r[i] = (uint32_t)c;
-    c >>= 32;
-  }
-  r[8] = (uint32_t)c;
-  U256 x;
-  for (int i = 0; i < 8; ++i) x.w[i] = r[i];
-  // subtract hi * q repeatedly: value = r8*2^256 + x; x < 2^256, r8 < L
-  // reduce via q's structure-free approach: while (r8 || x >= q) x -= q (with borrow into r8)
-  uint32_t hi = r[8];
-  while (hi != 0 || !lt256(x, q)) {
-    const uint32_t borrow = sub256(x, q);
-    hi -= borrow;
-  }
-  return x;
-}
-__device__ __forceinline__ U256 negmod(const U256& a, const U256& q) {  // (q - a) mod q, branch-free
-  uint32_t nz = 0;
-  for (int i = 0; i < 8; ++i) nz |= a.w[i];
-  U256 r = q;
-  sub256(r, a);
-  return sel256(0u - (uint32_t)(nz != 0), r, a);
-}
-
-// (a - b) mod q for a, b < q
-__device__ __forceinline__ U256 submod256(U256 a, const U256& b, const U256& q) {
-  const uint32_t borrow = sub256(a, b);
-  U256 t = a;
-  add256(t, q);
-  return sel256(0u - borrow, t, a);
-}
-// (a * b) mod q for a, b < q: left-to-right double-and-always-add with a masked select (one
-// thread; per proof, not per limb), so neither operand's bits steer the control flow
-__device__ __noinline__ U256 mulmod256(const U256& a, const U256& b, const U256& q) {
-  U256 r;
-  for (int k = 0; k < 8; ++k) r.w[k] = 0;
-  for (int bit = 255; bit >= 0; --bit) {
-    r = addmod256(r, r, q);
-    const U256 t = addmod256(r, b, q);
-    r = sel256(0u - ((a.w[bit >> 5] >> (bit & 31)) & 1u), t, r);
-  }
-  return r;
-}
-
-// Encryption scalars, one thread per selection (nonces n = (R, u, c_fake, v_fake)):
-//   s_fake = v_fake + R*c_fake, s_gneg = m ? c_fake : -c_fake, mscal = m   (mod q)
-// (known-nonce simulation of the fake branch: a_f = g^s_fake, b_f = K^s_fake g^(+-c_fake)).
-// plus (eg_ctx_set_proof_format EG_RESPONSE_PLUS: a = g^v X^-c): s_fake = v_fake - R*c_fake and
-// s_gneg = m ? -c_fake : c_fake.  The response convention is public; the vote stays masked.
-__global__ void k_enc_prep(const uint8_t* __restrict__ q_be, const uint8_t* __restrict__ votes,
-                           const uint8_t* __restrict__ nonces, uint32_t n, uint8_t* __restrict__ derived,
-                           uint32_t plus) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const U256 q = ld256(q_be);
-  const U256 R = ld256(nonces + ((size_t)i * 4 + 0) * 32);
-  const U256 cf = ld256(nonces + ((size_t)i * 4 + 2) * 32);
-  const U256 vf = ld256(nonces + ((size_t)i * 4 + 3) * 32);
-  const uint32_t m = votes[i] ? 1u : 0u;
-  const U256 Rc = mulmod256(R, cf, q);
-  const U256 sf = plus ? submod256(vf, Rc, q) : addmod256(vf, Rc, q);
-  // (m xor plus) ? c_fake : -c_fake, branch-free in the (secret) vote
-  const U256 sg = sel256((0u - m) ^ (0u - (plus & 1u)), cf, negmod(cf, q));
-  U256 ms;
-  for (int k = 0; k < 8; ++k) ms.w[k] = 0;
-  ms.w[0] = m;
-  st256(derived + ((size_t)i * 3 + 0) * 32, ms);
-  st256(derived + ((size_t)i * 3 + 1) * 32, sf);
-  st256(derived + ((size_t)i * 3 + 2) * 32, sg);
-}
-
-// R_sum per contest (one thread per contest): sum of the spc selection nonces R
-__global__ void k_enc_rsum(const uint8_t* __restrict__ q_be, const uint8_t* __restrict__ nonces, uint32_t ncon,
-                           uint32_t spc, uint8_t* __restrict__ rsum) {
-  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= ncon) return;
-  const U256 q = ld256(q_be);
-  U256 r;
-  for (int k = 0; k < 8; ++k) r.w[k] = 0;
-  for (uint32_t s = 0; s < spc; ++s) r = addmod256(r, ld256(nonces + (((size_t)j * spc + s) * 4) * 32), q);
-  st256(rsum + (size_t)j * 32, r);
-}
-
-// k_enc_rsum for a manifest of unequal contests: contest j = b * nc + k sums the len[k] selection
-// nonces R from selection b * nsel + first[k] on
-__global__ void k_enc_rsum_seg(const uint8_t* __restrict__ q_be, const uint8_t* __restrict__ nonces, uint32_t ncon,
-                               uint32_t nc, uint32_t nsel, const uint32_t* __restrict__ first,
-                               const uint32_t* __restrict__ len, uint8_t* __restrict__ rsum) {
-  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= ncon) return;
-  const U256 q = ld256(q_be);
-  const uint32_t b = j / nc, k = j % nc, n = len[k];
-  const size_t s0 = (size_t)b * nsel + first[k];
-  U256 r;
-  for (int w = 0; w < 8; ++w) r.w[w] = 0;
-  for (uint32_t s = 0; s < n; ++s) r = addmod256(r, ld256(nonces + ((s0 + s) * 4) * 32), q);
-  st256(rsum + (size_t)j * 32, r);
-}
-
-// Finish the range proofs: c_real = c - c_fake, v_real = u - c_real*R (plus: u + c_real*R); arrange by m.
-__global__ void k_enc_finish(const uint8_t* __restrict__ q_be, const uint8_t* __restrict__ votes,
-                             const uint8_t* __restrict__ nonces, const uint8_t* __restrict__ chal, uint32_t n,
-                             uint8_t* __restrict__ rproof, uint32_t plus) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const U256 q = ld256(q_be);
-  const U256 R = ld256(nonces + ((size_t)i * 4 + 0) * 32);
-  const U256 u = ld256(nonces + ((size_t)i * 4 + 1) * 32);
-  const U256 cf = ld256(nonces + ((size_t)i * 4 + 2) * 32);
-  const U256 vf = ld256(nonces + ((size_t)i * 4 + 3) * 32);
-  const U256 c = ld256(chal + (size_t)i * 32);
-  const U256 cr = submod256(c, cf, q);
-  const U256 cR = mulmod256(cr, R, q);
-  const U256 vr = plus ? addmod256(u, cR, q) : submod256(u, cR, q);
-  uint8_t* o = rproof + (size_t)i * 4 * 32;
-  const uint32_t mk = 0u - (uint32_t)(votes[i] != 0);  // the branch order follows the vote: masked
-  st256(o + 0, sel256(mk, cf, cr));
-  st256(o + 32, sel256(mk, vf, vr));
-  st256(o + 64, sel256(mk, cr, cf));
-  st256(o + 96, sel256(mk, vr, vf));
-}
-
-// Encryption commitments are computed vote-independently, real branch (a, b) in slots 0-1 and
-// the simulated branch in slots 2-3 of each selection's 4 commitment elements; this puts them in
-// proof order (branch 0 first), i.e. swaps the pairs where the vote is 1, with masks (the vote
-// is secret).  One thread per 4-word column of a selection's pair.
-__global__ void k_enc_order(uint32_t* __restrict__ comm, const uint8_t* __restrict__ votes, uint32_t n) {
-  constexpr uint32_t kQuads = 2 * kW / 4;  // a pair of elements, in uint4
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (size_t)n * kQuads) return;
-  const uint32_t i = (uint32_t)(t / kQuads), k = (uint32_t)(t % kQuads);
-  const uint32_t mk = 0u - (uint32_t)(votes[i] != 0);
-  uint4* lo = reinterpret_cast<uint4*>(comm + (size_t)i * 4 * kW) + k;
-  uint4* hi = lo + kQuads;
-  const uint4 a = *lo, b = *hi;
-  *lo = make_uint4((a.x & ~mk) | (b.x & mk), (a.y & ~mk) | (b.y & mk), (a.z & ~mk) | (b.z & mk),
-                   (a.w & ~mk) | (b.w & mk));
-  *hi = make_uint4((b.x & ~mk) | (a.x & mk), (b.y & ~mk) | (a.y & mk), (b.z & ~mk) | (a.z & mk),
-                   (b.w & ~mk) | (a.w & mk));
-}
-
-// Generic response v = u - c*x mod q (plus: u + c*x; x per item or shared when x_stride == 0);
-// writes proof (c, v) as 2 x 32 B.
-__global__ void k_response(const uint8_t* __restrict__ q_be, const uint8_t* __restrict__ u_be,
-                           const uint8_t* __restrict__ chal, const uint8_t* __restrict__ x_be, uint32_t x_stride,
-                           uint32_t n, uint8_t* __restrict__ proof, uint32_t plus) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const U256 q = ld256(q_be);
-  const U256 u = ld256(u_be + (size_t)i * 32);
-  const U256 c = ld256(chal + (size_t)i * 32);
-  const U256 x = ld256(x_be + (size_t)i * x_stride);
-  const U256 cx = mulmod256(c, x, q);
-  const U256 v = plus ? addmod256(u, cx, q) : submod256(u, cx, q);
-  st256(proof + (size_t)i * 64, c);
-  st256(proof + (size_t)i * 64 + 32, v);
-}
-
-// scalar derivation for the verifier (one thread per selection / contest)
-//   sel: out[i] = (q - c1_i) mod q  ; ok[i] = all of c0,v0,c1,v1 < q
-//   con: out[i] = (q - L*c_i mod q) ; ok[i] = c,v < q
-// plus (EG_RESPONSE_PLUS, a = g^v X^-c): out[i] = L*c_i mod q, and the proof words in neg_mask
-// (the challenges the variable bases are raised to) are negated in place, so the same job tables
-// compute X^-c; the Fiat-Shamir check then reads the caller's unmodified proofs.
-__device__ __forceinline__ void scalar_prep_item(const uint8_t* __restrict__ q_be, uint8_t* __restrict__ proofs,
-                                                 uint32_t i, uint32_t words_per, uint32_t neg_idx, uint32_t L,
-                                                 uint8_t* __restrict__ out, uint8_t* __restrict__ ok, uint32_t plus,
-                                                 uint32_t neg_mask) {
-  const U256 q = ld256(q_be);
-  bool good = true;
-  for (uint32_t k = 0; k < words_per; ++k) good &= lt256(ld256(proofs + ((size_t)i * words_per + k) * 32), q);
-  U256 c = ld256(proofs + ((size_t)i * words_per + neg_idx) * 32);
-  if (good) {
-    if (L != 1) c = mulsmall_mod(c, L, q);
-    if (!plus) c = negmod(c, q);
-    if (plus)
-      for (uint32_t k = 0; k < words_per; ++k)
-        if ((neg_mask >> k) & 1u) {
-          uint8_t* w = proofs + ((size_t)i * words_per + k) * 32;
-          st256(w, negmod(ld256(w), q));
-        }
-  } else {
-    for (int k = 0; k < 8; ++k) c.w[k] = 0;
-  }
-  st256(out + (size_t)i * 32, c);
-  ok[i] = good ? 1 : 0;
-}
-
-__global__ void k_scalar_prep(const uint8_t* __restrict__ q_be, uint8_t* __restrict__ proofs,
-                              uint32_t n, uint32_t words_per, uint32_t neg_idx, uint32_t L,
-                              uint8_t* __restrict__ out, uint8_t* __restrict__ ok, uint32_t plus,
-                              uint32_t neg_mask) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  scalar_prep_item(q_be, proofs, i, words_per, neg_idx, L, out, ok, plus, neg_mask);
-}
-
-// the contest form for a manifest of unequal contests: item i (contest i % period of its ballot)
-// takes its selection limit L from Ltab[i % period]
-__global__ void k_scalar_prep_tab(const uint8_t* __restrict__ q_be, uint8_t* __restrict__ proofs,
-                                  uint32_t n, uint32_t words_per, uint32_t neg_idx,
-                                  const uint32_t* __restrict__ Ltab, uint32_t period,
-                                  uint8_t* __restrict__ out, uint8_t* __restrict__ ok, uint32_t plus,
-                                  uint32_t neg_mask) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  scalar_prep_item(q_be, proofs, i, words_per, neg_idx, Ltab[i % period], out, ok, plus, neg_mask);
-}
-
-// ---------------------------------------------------------------------------------
-// Fiat-Shamir hash + compare (one thread per proof).
-//   H = SHA256("|" + hex(e_0) + "|" + ... + "|") mod q, hex upper-case, fixed width or
-//   minimal-length per hash_minimal (eg_ctx_set_hash_format).
-//   selection: elements (qbar, alpha, beta, a0, b0, a1, b1), expect (c0 + c1) mod q
-//   contest  : elements (qbar, A, B, a, b),                   expect c
-// (the elements after qbar in the ctx's pre-image order, eg_ctx_set_proof_format; up to 8 sources;
-// a source of stride 0 is one element shared by every proof, e.g. the election key K)
-// ---------------------------------------------------------------------------------
-struct HashSrc {
-  const uint8_t* ptr;  // base pointer
-  uint32_t bytes;      // element width (32 or 512)
-  uint32_t stride;     // bytes between consecutive proofs' elements
-};
-
-__global__ void __launch_bounds__(kBlock) k_hash_check(const uint8_t* __restrict__ q_be,
-                                                       const uint8_t* __restrict__ qbar_be, uint32_t n,
-                                                       uint32_t nsrc, HashSrc s0, HashSrc s1, HashSrc s2,
-                                                       HashSrc s3, HashSrc s4, HashSrc s5, HashSrc s6, HashSrc s7,
-                                                       const uint8_t* __restrict__ proofs,
-                                                       uint32_t proof_words, uint32_t cidx0, uint32_t cidx1,
-                                                       const uint8_t* __restrict__ pre_ok,
-                                                       const uint8_t* __restrict__ pre_ok2, uint32_t pre2_div,
-                                                       uint8_t* __restrict__ ok, uint8_t* __restrict__ out_h,
-                                                       uint32_t hash_minimal) {
-  // one 64-B block buffer per thread, at a 68-B stride: with a 64-B stride every lane's
-  // byte k sits in the same LDS bank and each buffer access is a 32-way conflict
-  constexpr int kBufStride = 17;
-  __shared__ uint32_t s_buf[kBlock * kBufStride];
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  Sha256 H;
-  H.init(s_buf + threadIdx.x * kBufStride);
-  H.put('|');
-  H.put_hex(qbar_be, 32, hash_minimal != 0);
-  H.put('|');
-  const HashSrc src[8] = {s0, s1, s2, s3, s4, s5, s6, s7};
-  for (uint32_t k = 0; k < nsrc; ++k) {
-    H.put_hex(src[k].ptr + (size_t)i * src[k].stride, src[k].bytes, hash_minimal != 0);
-    H.put('|');
-  }
-  uint32_t dig[8];
-  H.finish(dig);
-  const U256 q = ld256(q_be);
-  U256 h;
-  for (int k = 0; k < 8; ++k) h.w[k] = dig[7 - k];
-  if (!lt256(h, q)) sub256(h, q);
-  if (out_h) st256(out_h + (size_t)i * 32, h);
-  if (!ok) return;
-  U256 c = ld256(proofs + ((size_t)i * proof_words + cidx0) * 32);
-  if (cidx1 != kNone) c = addmod256(c, ld256(proofs + ((size_t)i * proof_words + cidx1) * 32), q);
-  bool good = true;
-  for (int k = 0; k < 8; ++k) good &= (c.w[k] == h.w[k]);
-  if (pre_ok) good &= pre_ok[i] != 0;
-  if (pre_ok2) {
-    // pre_ok2 indexed per element pair: both pad/data of selection i must be < p
-    good &= pre_ok2[(size_t)i * pre2_div] != 0 && pre_ok2[(size_t)i * pre2_div + 1] != 0;
-  }
-  ok[i] = good ? 1 : 0;
+  return diff;
 }
 
 }  // namespace eg

@@ -12,46 +12,29 @@
 // ciphertexts per ballot (soff_k the contest's first) and T = sum limit_k vectors (toff_k).
 //
 // Conventions are eg_codes.hpp's: one thread per item, 256 threads per block, 64-bit indices, no
-// barrier, hashes through eg::Sha256 on the 17-word LDS stride.  Every loop reads its operands
-// from memory: there is no local array, so nothing goes to scratch.
+// barrier, hashes through eg_hash_elems.hpp's HashElems (closed by mod_q_top), scalars through
+// eg_u256.hpp, byte rows through eg_kernels.hpp's row helpers.  Every loop reads its operands from
+// memory: there is no local array, so nothing goes to scratch.
 #pragma once
-#include "eg_codes.hpp"
+#include "eg_hash_elems.hpp"
+#include "eg_kernels.hpp"
+#include "eg_u256.hpp"
 
 namespace eg {
-
-__device__ __forceinline__ bool eq256(const U256& a, const U256& b) {
-  uint32_t d = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) d |= a.w[i] ^ b.w[i];
-  return d == 0;
-}
 
 // mask of a short code: the low code_bytes bytes of psi's last word
 __device__ __forceinline__ uint32_t code_mask(uint32_t code_bytes) {
   return code_bytes >= 4 ? 0xFFFFFFFFu : ((1u << (8 * code_bytes)) - 1u);
 }
 
-// rho = H(xi, 4, w)
-__device__ __forceinline__ U256 pre_rho(uint32_t* lds, const uint8_t* __restrict__ xi, uint32_t w, bool mn,
-                                        const uint8_t* __restrict__ q_be) {
-  Sha256 H;
-  H.init(lds);
-  H.put('|');
-  H.put_hex(xi, 32, mn);
-  H.put('|');
-  put_hex_small(H, 4u, mn);
-  H.put('|');
-  put_hex_small(H, w, mn);
-  H.put('|');
-  return finish_mod_q(H, q_be);
-}
-
-__device__ __forceinline__ U256 small256(uint32_t v) {
-  U256 r;
-  r.w[0] = v;
-#pragma unroll
-  for (int i = 1; i < 8; ++i) r.w[i] = 0;
-  return r;
+// rho = H(xi, 4, w), on the block's buffer s_buf
+__device__ __forceinline__ U256 pre_rho(uint32_t* s_buf, const uint8_t* __restrict__ xi, uint32_t w,
+                                        uint32_t hash_minimal, const uint8_t* __restrict__ q_be) {
+  HashElems H(s_buf, hash_minimal);
+  H.q(xi);
+  H.small(4u);
+  H.small(w);
+  return H.mod_q_top(ld256(q_be));
 }
 
 // One thread per (b, w): rho[b,w] and the diagonal scalar [i = j] (diag: V flags, one per
@@ -60,32 +43,26 @@ __global__ void __launch_bounds__(256) k_pre_nonces(const uint8_t* __restrict__ 
                                                     const uint8_t* __restrict__ ballot_nonces, uint64_t nb, uint32_t V,
                                                     const uint32_t* __restrict__ diag, uint8_t* __restrict__ rho,
                                                     uint8_t* __restrict__ unit, uint32_t hash_minimal) {
-  __shared__ uint32_t s_buf[256 * kCodeBufStride];
+  __shared__ uint32_t s_buf[256 * kHashBufStride];
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= nb * V) return;
   const uint64_t b = i / V;
   const uint32_t w = (uint32_t)(i - b * V);
-  st256(rho + i * 32,
-        pre_rho(s_buf + threadIdx.x * kCodeBufStride, ballot_nonces + b * 32, w, hash_minimal != 0, q_be));
-  st256(unit + i * 32, small256(diag[w]));
+  st256(rho + i * 32, pre_rho(s_buf, ballot_nonces + b * 32, w, hash_minimal, q_be));
+  st256(unit + i * 32, u256_small(diag[w]));
 }
 
 // One thread per ciphertext: e = H(P alpha, P beta); cts (n, 2, 512).
 __global__ void __launch_bounds__(256) k_pre_comp_hash(const uint8_t* __restrict__ q_be,
                                                        const uint8_t* __restrict__ cts, uint64_t n,
                                                        uint8_t* __restrict__ out, uint32_t hash_minimal) {
-  __shared__ uint32_t s_buf[256 * kCodeBufStride];
+  __shared__ uint32_t s_buf[256 * kHashBufStride];
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const bool mn = hash_minimal != 0;
-  Sha256 H;
-  H.init(s_buf + threadIdx.x * kCodeBufStride);
-  H.put('|');
-  H.put_hex(cts + i * 1024, 512, mn);
-  H.put('|');
-  H.put_hex(cts + i * 1024 + 512, 512, mn);
-  H.put('|');
-  st256(out + i * 32, finish_mod_q(H, q_be));
+  HashElems H(s_buf, hash_minimal);
+  H.p(cts + i * 1024);
+  H.p(cts + i * 1024 + 512);
+  st256(out + i * 32, H.mod_q_top(ld256(q_be)));
 }
 
 // One thread per row: dst[i] = src[idx[i]], 32-byte rows (dcon expanded to one row per vector,
@@ -144,7 +121,7 @@ __global__ void __launch_bounds__(256) k_pre_rec_nonces(const uint8_t* __restric
                                                         const uint32_t* __restrict__ spc,
                                                         const uint32_t* __restrict__ voff, uint8_t* __restrict__ rho,
                                                         uint8_t* __restrict__ unit, uint32_t hash_minimal) {
-  __shared__ uint32_t s_buf[256 * kCodeBufStride];
+  __shared__ uint32_t s_buf[256 * kHashBufStride];
   const uint64_t it = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (it >= nb * S) return;
   const uint64_t b = it / S;
@@ -160,9 +137,8 @@ __global__ void __launch_bounds__(256) k_pre_rec_nonces(const uint8_t* __restric
     seen += set;
   }
   const uint32_t w = voff[k] + i * m + j;
-  st256(rho + it * 32,
-        pre_rho(s_buf + threadIdx.x * kCodeBufStride, ballot_nonces + b * 32, w, hash_minimal != 0, q_be));
-  st256(unit + it * 32, small256(i == j ? 1u : 0u));
+  st256(rho + it * 32, pre_rho(s_buf, ballot_nonces + b * 32, w, hash_minimal, q_be));
+  st256(unit + it * 32, u256_small(i == j ? 1u : 0u));
 }
 
 // One thread per (b, slot s): the recorded ballot's encryption nonce of slot off_k + j,
@@ -183,7 +159,7 @@ __global__ void __launch_bounds__(256) k_pre_rec_sums(const uint8_t* __restrict_
   const uint32_t s = (uint32_t)(it - b * nsel);
   const uint32_t k = kof[s], m = spc[k], j = s - off[k];
   const U256 q = ld256(q_be);
-  U256 r = small256(0);
+  U256 r = u256_zero();
   for (uint32_t t = 0; t < limit[k]; ++t) r = addmod256(r, ld256(rho + (b * S + soff[k] + t * m + j) * 32), q);
   st256(sel_nonces + it * 128, r);
 }
@@ -264,13 +240,7 @@ __global__ void __launch_bounds__(256) k_pre_nonzero(const uint8_t* __restrict__
                                                      uint8_t* __restrict__ flags) {
   const uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= n) return;
-  const uint4* s = reinterpret_cast<const uint4*>(be + e * 512);
-  uint32_t any = 0;
-  for (int i = 0; i < 32; ++i) {
-    const uint4 v = s[i];
-    any |= v.x | v.y | v.z | v.w;
-  }
-  if (!any) flags[e] = 0;
+  if (row512_or(be + e * 512, ~0u, 0u) == 0) flags[e] = 0;
 }
 
 // One thread per (b, k), the verdict of the pre-encryption check:
@@ -310,14 +280,8 @@ __global__ void __launch_bounds__(256) k_pre_verify(const uint8_t* __restrict__ 
     good &= eq256(a, ld256(sorted + (row + (r < m ? r : 0u)) * 32));
     good &= sel_codes[trow + t] == (a.w[0] & cm);
   }
-  const uint4* x4 = reinterpret_cast<const uint4*>(prod + row * 1024);
-  const uint4* y4 = reinterpret_cast<const uint4*>(cts + row * 1024);
-  uint32_t diff = 0;
-  for (uint32_t i = 0; i < m * 64; ++i) {
-    const uint4 x = x4[i], y = y4[i];
-    diff |= (x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w);
-  }
-  good &= diff == 0;
+  good &= quads_diff(reinterpret_cast<const uint4*>(prod + row * 1024),
+                     reinterpret_cast<const uint4*>(cts + row * 1024), (uint64_t)m * 64) == 0;
   ok[it] = good ? 1 : 0;
 }
 

@@ -1,27 +1,17 @@
 // eg_range.hpp — the scalar, hash and ordering kernels of the 0..L range proof
 // (include/eg_hip_range.h).  The exponentiations are k_pow jobs (eg_kernels.hpp);
 // these kernels run one thread per item with 256-thread workgroups, 64-bit item indices and no
-// barrier, like the scalar kernels of eg_kernels.hpp.
+// barrier, like the scalar kernels of eg_proof_kernels.hpp; scalars are eg_u256.hpp's,
+// the pre-image writer eg_hash_elems.hpp's.
 //
 // An item's proof is B = L + 1 branches (c_j, v_j), 2 B scalars of 32 bytes; its commitments are
 // 2 B consecutive elements (a_0, b_0, ..., a_L, b_L).
 #pragma once
+#include "eg_hash_elems.hpp"
 #include "eg_kernels.hpp"
+#include "eg_u256.hpp"
 
 namespace eg {
-
-// (k * a) mod q for a < q and k < 256, on a fixed schedule of eight doublings and eight masked
-// additions: neither k (the prover's value m) nor a steers a branch.
-__device__ __forceinline__ U256 mulbyte_mod(const U256& a, uint32_t k, const U256& q) {
-  U256 r;
-  for (int w = 0; w < 8; ++w) r.w[w] = 0;
-  for (int bit = 7; bit >= 0; --bit) {
-    r = addmod256(r, r, q);
-    const U256 t = addmod256(r, a, q);
-    r = sel256(0u - ((k >> bit) & 1u), t, r);
-  }
-  return r;
-}
 
 // Verifier scalars of item i from its proof row (a working copy: the hash reads the caller's).
 //   e_j = c_j, or -c_j in place under EG_RESPONSE_PLUS (the comb exponents of alpha and beta);
@@ -39,8 +29,7 @@ __global__ void __launch_bounds__(kBlock) k_range_scalars(const uint8_t* __restr
   bool good = true;
   for (uint32_t k = 0; k < 2 * B; ++k) good &= lt256(ld256(row + (size_t)k * 32), q);
   for (uint32_t j = 0; j < B; ++j) {
-    U256 g;
-    for (int w = 0; w < 8; ++w) g.w[w] = 0;
+    U256 g = u256_zero();
     if (good) {
       U256 e = ld256(row + (size_t)j * 64);
       if (plus) {
@@ -118,8 +107,7 @@ __global__ void __launch_bounds__(kBlock) k_range_finish(const uint8_t* __restri
   const U256 q = ld256(q_be);
   const uint32_t m = values[i];
   const uint8_t* nrow = nonces + i * (2 * B + 1) * 32;
-  U256 zero;
-  for (int w = 0; w < 8; ++w) zero.w[w] = 0;
+  const U256 zero = u256_zero();
   U256 sum = zero;
   for (uint32_t j = 0; j < B; ++j) {
     const U256 c = ld256(nrow + 32 + (size_t)j * 64);
@@ -148,7 +136,7 @@ __global__ void __launch_bounds__(kBlock) k_range_finish(const uint8_t* __restri
 //                        (the scalar flag of k_range_scalars; the range and residue flags of
 //                        alpha and beta, k_import / k_resid_check); proofs are the caller's rows
 //   out_h != null (prove): out_h[i] = H
-// The 64-byte block buffer sits in LDS at a 17-word stride per thread (k_hash_check).
+// The digest is closed as k_hash_check's: mod_q_top, the production q.
 __global__ void __launch_bounds__(kBlock) k_range_hash(const uint8_t* __restrict__ q_be,
                                                        const uint8_t* __restrict__ qbar_be, uint64_t n, uint32_t L,
                                                        const uint8_t* __restrict__ cts,
@@ -158,18 +146,14 @@ __global__ void __launch_bounds__(kBlock) k_range_hash(const uint8_t* __restrict
                                                        const uint8_t* __restrict__ sc_ok,
                                                        const uint8_t* __restrict__ ltp, uint8_t* __restrict__ ok,
                                                        uint8_t* __restrict__ out_h, uint32_t hash_minimal) {
-  constexpr int kBufStride = 17;
-  __shared__ uint32_t s_buf[kBlock * kBufStride];
+  __shared__ uint32_t s_buf[kBlock * kHashBufStride];
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint32_t B = L + 1, ncomm = 2 * B;
   const uint8_t* msg = cts + i * 1024;
   const uint8_t* cm = comm + i * ncomm * 512;
-  Sha256 H;
-  H.init(s_buf + threadIdx.x * kBufStride);
-  H.put('|');
-  H.put_hex(qbar_be, 32, hash_minimal != 0);
-  H.put('|');
+  HashElems H(s_buf, hash_minimal);
+  H.q(qbar_be);
   const uint32_t lead = order == 2u ? 1u : 0u;  // EG_PREIMAGE_WITH_KEY
   const uint32_t nel = lead + 2 + ncomm;
   for (uint32_t k = 0; k < nel; ++k) {
@@ -181,21 +165,15 @@ __global__ void __launch_bounds__(kBlock) k_range_hash(const uint8_t* __restrict
       if (order == 1u) src = e < ncomm ? cm + (size_t)e * 512 : msg + (size_t)(e - ncomm) * 512;  // commitments first
       else src = e < 2 ? msg + (size_t)e * 512 : cm + (size_t)(e - 2) * 512;
     }
-    H.put_hex(src, 512, hash_minimal != 0);
-    H.put('|');
+    H.p(src);
   }
-  uint32_t dig[8];
-  H.finish(dig);
   const U256 q = ld256(q_be);
-  U256 h;
-  for (int k = 0; k < 8; ++k) h.w[k] = dig[7 - k];
-  if (!lt256(h, q)) sub256(h, q);
+  const U256 h = H.mod_q_top(q);
   if (out_h) st256(out_h + i * 32, h);
   if (!ok) return;
   U256 c = ld256(proofs + i * B * 64);
   for (uint32_t j = 1; j < B; ++j) c = addmod256(c, ld256(proofs + i * B * 64 + (size_t)j * 64), q);
-  bool good = true;
-  for (int k = 0; k < 8; ++k) good &= (c.w[k] == h.w[k]);
+  bool good = eq256(c, h);
   good &= sc_ok[i] != 0 && ltp[i * 2] != 0 && ltp[i * 2 + 1] != 0;
   ok[i] = good ? 1 : 0;
 }

@@ -2,64 +2,34 @@
 // mix, prover and verifier (include/eg_hip_shuffle.h).  DESIGN §11's conventions: one
 // thread per item (one 8-lane group per element in the Montgomery kernel), 256 threads per block,
 // 64-bit indices; only the scan and the dot use a block barrier.  The powers and the products are
-// k_pow, k_prod, k_mul and k_pp_* (eg_kernels.hpp, eg_prodpow.hpp).
+// k_pow, k_prod, k_mul and k_pp_* (eg_kernels.hpp, eg_prodpow.hpp); the mix's nonces are reduced
+// mod q by k_reduce_q and the generator seed is hashed by k_hash_check (eg_proof_kernels.hpp).
+// Scalars are eg_u256.hpp's, the pre-image writer eg_hash_elems.hpp's.
 #pragma once
 
-#include "eg_decrypt2.hpp"
+#include "eg_hash_elems.hpp"
 #include "eg_kernels.hpp"
+#include "eg_u256.hpp"
 
 namespace eg {
-
-// the hex of the Q element of a value below 2^32, in the context's format: 56 zeros and 8 digits,
-// or the value's bytes without leading zero bytes (at least one)
-__device__ __forceinline__ void sh_put_small(Sha256& H, uint32_t v, bool minimal) {
-  int nb = 4;
-  if (minimal) {
-    nb = 1;
-    while (nb < 4 && (v >> (8 * nb)) != 0) ++nb;
-  } else {
-    for (int i = 0; i < 14; ++i) H.put4(0x30303030u);
-  }
-  for (int b = nb - 1; b >= 0; --b) {
-    const uint32_t byte = (v >> (8 * b)) & 0xFFu;
-    H.put(Sha256::hexc(byte >> 4));
-    H.put(Sha256::hexc(byte & 15u));
-  }
-}
 
 // X[k] = D[k,0] || ... || D[k,15], D[k,t] = SHA-256("|gseed|43|k|t|") raw: item i = 16 k + t
 // writes its 32 bytes at X + 32 i (gseed: 32 bytes in HBM, 16-byte aligned)
 __global__ void __launch_bounds__(kBlock) k_sh_expand(const uint8_t* __restrict__ gseed, uint32_t tag, uint64_t items,
                                                       uint32_t hash_minimal, uint8_t* __restrict__ X) {
-  constexpr int kBufStride = 17;  // k_hash_check's: a 64-byte stride puts every lane in one LDS bank
-  __shared__ uint32_t s_buf[kBlock * kBufStride];
+  __shared__ uint32_t s_buf[kBlock * kHashBufStride];
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= items) return;
-  const bool minimal = hash_minimal != 0;
-  Sha256 H;
-  H.init(s_buf + threadIdx.x * kBufStride);
-  H.put('|');
-  H.put_hex(gseed, 32, minimal);
-  H.put('|');
-  sh_put_small(H, tag, minimal);
-  H.put('|');
-  sh_put_small(H, (uint32_t)(i >> 4), minimal);
-  H.put('|');
-  sh_put_small(H, (uint32_t)(i & 15u), minimal);
-  H.put('|');
+  HashElems H(s_buf, hash_minimal);
+  H.q(gseed);
+  H.small(tag);
+  H.small((uint32_t)(i >> 4));
+  H.small((uint32_t)(i & 15u));
   uint32_t dig[8];
-  H.finish(dig);
+  H.digest(dig);
   uint32_t* out = reinterpret_cast<uint32_t*>(X + i * 32);
 #pragma unroll
   for (int k = 0; k < 8; ++k) out[k] = __builtin_bswap32(dig[k]);
-}
-
-// out[i] = in[i] mod q  (the mix's nonces; in is left as the caller gave it)
-__global__ void __launch_bounds__(kBlock) k_sh_reduce(const uint8_t* __restrict__ q_be, const uint8_t* __restrict__ in,
-                                                      uint64_t n, uint8_t* __restrict__ out) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  st256(out + i * 32, d2_modq(ld256(in + i * 32), ld256(q_be)));
 }
 
 // flag |= 1 if a canonical 512-byte row is 0 or 1 (a generator that generates nothing)
@@ -67,16 +37,7 @@ __global__ void __launch_bounds__(kBlock) k_sh_trivial(const uint8_t* __restrict
                                                        uint32_t* __restrict__ flag) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const uint4* r = reinterpret_cast<const uint4*>(rows + i * 512);
-  uint32_t any = 0;
-#pragma unroll 4
-  for (int t = 0; t < 31; ++t) {
-    const uint4 v = r[t];
-    any |= v.x | v.y | v.z | v.w;
-  }
-  const uint4 v = r[31];
-  any |= v.x | v.y | v.z | (v.w & 0x00FFFFFFu) | ((v.w >> 24) & 0xFEu);  // the last byte may be 0 or 1
-  if (any == 0) atomicOr(flag, 1u);
+  if (row512_or(rows + i * 512, ~0x01000000u, 0u) == 0) atomicOr(flag, 1u);  // the last byte may be 0 or 1
 }
 
 // out[i] = in[min(psi[i / per], rows - 1) * per + i % per] * x[i]  (Montgomery form; per elements
@@ -102,75 +63,44 @@ __global__ void __launch_bounds__(kBlock) k_sh_gather_mul(const MontConsts* __re
 }
 
 // ---------------------------------------------------------------------------------
-// the proof's hashes: "|hex|...|" in the context's format, SHA-256, mod q
+// the proof's hashes: hash_elems in the context's format, closed by mod_q_any (a test group's q
+// may be far below 2^256)
 // ---------------------------------------------------------------------------------
-__device__ __forceinline__ U256 sh_finish_modq(Sha256& H, const U256& q) {
-  uint32_t dig[8];
-  H.finish(dig);
-  U256 h;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) h.w[k] = dig[7 - k];
-  if (!lt256(h, q)) {
-    sub256(h, q);
-    if (!lt256(h, q)) h = d2_modq(h, q);  // a q far below 2^256 (test groups)
-  }
-  return h;
-}
-
 // leaf[i] = H(Q 0x40, P x_0, ..., P x_{m-1}) of row i's m elements (512-byte rows, 16-byte aligned)
 __global__ void __launch_bounds__(kBlock) k_sh_leaf(const uint8_t* __restrict__ q_be, const uint8_t* __restrict__ rows,
                                                     uint64_t m, uint64_t n, uint32_t hash_minimal,
                                                     uint8_t* __restrict__ out) {
-  constexpr int kBufStride = 17;
-  __shared__ uint32_t s_buf[kBlock * kBufStride];
+  __shared__ uint32_t s_buf[kBlock * kHashBufStride];
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const bool minimal = hash_minimal != 0;
-  Sha256 H;
-  H.init(s_buf + threadIdx.x * kBufStride);
-  H.put('|');
-  sh_put_small(H, 0x40u, minimal);
-  H.put('|');
-  for (uint64_t k = 0; k < m; ++k) {
-    H.put_hex(rows + (i * m + k) * 512, 512, minimal);
-    H.put('|');
-  }
-  st256(out + i * 32, sh_finish_modq(H, ld256(q_be)));
+  HashElems H(s_buf, hash_minimal);
+  H.small(0x40u);
+  for (uint64_t k = 0; k < m; ++k) H.p(rows + (i * m + k) * 512);
+  st256(out + i * 32, H.mod_q_any(ld256(q_be)));
 }
 
 // one level of T: out[c] = H(Q 0x41, Q len, Q v_0, ...) of chunk c's len <= 256 values of in (n in all)
 __global__ void __launch_bounds__(kBlock) k_sh_tree(const uint8_t* __restrict__ q_be, const uint8_t* __restrict__ in,
                                                     uint64_t n, uint32_t hash_minimal, uint8_t* __restrict__ out) {
-  constexpr int kBufStride = 17;
-  __shared__ uint32_t s_buf[kBlock * kBufStride];
+  __shared__ uint32_t s_buf[kBlock * kHashBufStride];
   const uint64_t ch = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (ch * 256 >= n) return;
-  const bool minimal = hash_minimal != 0;
   const uint32_t len = (uint32_t)(n - ch * 256 < 256 ? n - ch * 256 : 256);
-  Sha256 H;
-  H.init(s_buf + threadIdx.x * kBufStride);
-  H.put('|');
-  sh_put_small(H, 0x41u, minimal);
-  H.put('|');
-  sh_put_small(H, len, minimal);
-  H.put('|');
-  for (uint32_t k = 0; k < len; ++k) {
-    H.put_hex(in + (ch * 256 + k) * 32, 32, minimal);
-    H.put('|');
-  }
-  st256(out + ch * 32, sh_finish_modq(H, ld256(q_be)));
+  HashElems H(s_buf, hash_minimal);
+  H.small(0x41u);
+  H.small(len);
+  for (uint32_t k = 0; k < len; ++k) H.q(in + (ch * 256 + k) * 32);
+  st256(out + ch * 32, H.mod_q_any(ld256(q_be)));
 }
 
-__device__ __forceinline__ U256 sh_challenge(Sha256& H, const uint8_t* __restrict__ y, uint32_t j, bool minimal,
-                                             const U256& q) {
-  H.put('|');
-  H.put_hex(y, 32, minimal);
-  H.put('|');
-  sh_put_small(H, 0x44u, minimal);
-  H.put('|');
-  sh_put_small(H, j, minimal);
-  H.put('|');
-  return sh_finish_modq(H, q);
+// H(Q y, Q 0x44, Q j), on the block's buffer s_buf
+__device__ __forceinline__ U256 sh_challenge(uint32_t* s_buf, const uint8_t* __restrict__ y, uint32_t j,
+                                             uint32_t hash_minimal, const U256& q) {
+  HashElems H(s_buf, hash_minimal);
+  H.q(y);
+  H.small(0x44u);
+  H.small(j);
+  return H.mod_q_any(q);
 }
 
 // u[j] = H(Q y, Q 0x44, Q j); with psi also up[i] = u[psi(i)], hashed again instead of gathered
@@ -179,18 +109,12 @@ __global__ void __launch_bounds__(kBlock) k_sh_challenges(const uint8_t* __restr
                                                           const uint32_t* __restrict__ psi, uint64_t n,
                                                           uint32_t hash_minimal, uint8_t* __restrict__ u,
                                                           uint8_t* __restrict__ up) {
-  constexpr int kBufStride = 17;
-  __shared__ uint32_t s_buf[kBlock * kBufStride];
+  __shared__ uint32_t s_buf[kBlock * kHashBufStride];
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const U256 q = ld256(q_be);
-  Sha256 H;
-  H.init(s_buf + threadIdx.x * kBufStride);
-  st256(u + i * 32, sh_challenge(H, y, (uint32_t)i, hash_minimal != 0, q));
-  if (psi != nullptr) {
-    H.init(s_buf + threadIdx.x * kBufStride);
-    st256(up + i * 32, sh_challenge(H, y, min(psi[i], (uint32_t)(n - 1)), hash_minimal != 0, q));
-  }
+  st256(u + i * 32, sh_challenge(s_buf, y, (uint32_t)i, hash_minimal, q));
+  if (psi != nullptr) st256(up + i * 32, sh_challenge(s_buf, y, min(psi[i], (uint32_t)(n - 1)), hash_minimal, q));
 }
 
 // inv[psi(i)] = i  (inv zeroed before; an entry >= n counts as n - 1)
@@ -204,20 +128,6 @@ __global__ void __launch_bounds__(kBlock) k_sh_invert(const uint32_t* __restrict
 // ---------------------------------------------------------------------------------
 // the proof's scalars
 // ---------------------------------------------------------------------------------
-__device__ __forceinline__ U256 sh_one() {
-  U256 r;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) r.w[k] = 0;
-  r.w[0] = 1;
-  return r;
-}
-__device__ __forceinline__ U256 sh_zero() {
-  U256 r;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) r.w[k] = 0;
-  return r;
-}
-
 // One level of the scan of the affine maps x -> A x + B mod q (composition is associative): every
 // block replaces its 256 maps by their inclusive compositions (Hillis-Steele in LDS, 8 steps) and
 // writes the block's total to tot[block].  In place: A, B hold the maps in and the prefixes out.
@@ -228,7 +138,7 @@ __global__ void __launch_bounds__(kBlock) k_sh_scan(const uint8_t* __restrict__ 
   const uint32_t t = threadIdx.x;
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + t;
   const U256 q = ld256(q_be);
-  U256 a = sh_one(), b = sh_zero();
+  U256 a = u256_small(1), b = u256_zero();
   if (i < n) a = ld256(A + i * 32), b = ld256(B + i * 32);
   for (uint32_t d = 1; d < kBlock; d <<= 1) {
     sa[t] = a;
@@ -269,7 +179,7 @@ __global__ void __launch_bounds__(kBlock) k_sh_dot(const uint8_t* __restrict__ q
   const uint32_t t = threadIdx.x;
   const uint64_t col = blockIdx.x, i = (uint64_t)blockIdx.y * blockDim.x + t;
   const U256 q = ld256(q_be);
-  U256 v = PROD ? sh_one() : sh_zero();
+  U256 v = u256_small(PROD ? 1u : 0u);
   if (i < n) {
     v = ld256(a + (col * cs + i * is) * 32);
     if (b != nullptr) v = mulmod256(v, ld256(b + i * 32), q);
@@ -302,7 +212,7 @@ __global__ void __launch_bounds__(kBlock) k_sh_neg(const uint8_t* __restrict__ q
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const U256 q = ld256(q_be);
-  st256(out + i * 32, negmod(d2_modq(ld256(in + i * 32), q), q));
+  st256(out + i * 32, negmod(mod256_any(ld256(in + i * 32), q), q));
 }
 
 // ---------------------------------------------------------------------------------
@@ -321,16 +231,7 @@ __global__ void __launch_bounds__(kBlock) k_sh_resid(const uint8_t* __restrict__
                                                      uint64_t n, uint32_t* __restrict__ flag) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const uint4* r = reinterpret_cast<const uint4*>(pw + i * 512);
-  uint32_t any = 0;
-#pragma unroll 4
-  for (int t = 0; t < 31; ++t) {
-    const uint4 v = r[t];
-    any |= v.x | v.y | v.z | v.w;
-  }
-  const uint4 v = r[31];
-  any |= v.x | v.y | v.z | (v.w ^ 0x01000000u);  // big-endian 1
-  if (any != 0 || lt_p[i] == 0) atomicOr(flag, 2u);
+  if (row512_or(pw + i * 512, ~0u, 0x01000000u) != 0 || lt_p[i] == 0) atomicOr(flag, 2u);  // big-endian 1
 }
 
 // mask = flag | (4 unless c' == c); ok = mask == 0
@@ -338,11 +239,7 @@ __global__ void k_sh_verdict(const uint8_t* __restrict__ c_given, const uint8_t*
                              const uint32_t* __restrict__ flag, uint8_t* __restrict__ ok,
                              uint32_t* __restrict__ mask) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  const U256 a = ld256(c_given), b = ld256(c_made);
-  uint32_t diff = 0;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) diff |= a.w[k] ^ b.w[k];
-  const uint32_t m = *flag | (diff != 0 ? 4u : 0u);
+  const uint32_t m = *flag | (eq256(ld256(c_given), ld256(c_made)) ? 0u : 4u);
   *mask = m;
   *ok = m == 0 ? 1 : 0;
 }

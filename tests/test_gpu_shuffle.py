@@ -404,6 +404,48 @@ def test_proof_across_blocks(group, large, large_proof):
             (False, R.CHALLENGE), (name, i)
 
 
+def test_proof_in_the_minimal_format_against_cpython(group):
+    """N = 257, w = 1 with hash_format = "minimal": the small-integer elements of the proof's hashes
+    (the tags and the `len` of k_sh_leaf and k_sh_tree, the index of k_sh_challenges) in the format
+    the generators alone were checked in.  257 is the smallest N with a second tree level: a node of
+    len 256 (two hex bytes in minimal form) beside a node of len 1, and challenge indices on both
+    sides of 255 -> 256.  Every output of the prover against shuffle_ref.prove(fmt="minimal").
+    The rows and generators are g^x by the fixed-base path (G is an argument), and rho, omega^,
+    omega', r are below 2^32, so that CPython's full-size powers are the chain's 2 N only; rho^ and
+    omega_1..4 are full-size, and every response is."""
+    from electionguard import shuffle as S
+    p, q, g, N = group.p, group.q, group.g, 257
+    rng = random.Random(257)
+    K = pow(g, rng.randrange(1, q), p)
+    rows = group.gPowP_batch([rng.randrange(q) for _ in range(2 * N)]).reshape(N, 1, 2, 512)
+    k = [rng.randrange(1, q) for _ in range(N + 1)]
+    Gb = group.gPowP_batch(k + [sum(k[1:]) % q])        # h, h_1 .. h_N and their product
+    E, G = S.rows_to_ints(rows), ints(Gb)
+    psi = list(range(N))
+    rng.shuffle(psi)
+    r = [[rng.randrange(1 << 32)] for _ in range(N)]
+    E2 = R.mix(p, q, g, K, E, psi, r)
+    small = lambda n: [rng.randrange(1 << 32) for _ in range(n)]
+    nonces = small(N) + [rng.randrange(q) for _ in range(N)] + small(2 * N) + [rng.randrange(q) for _ in range(4)]
+    want = R.prove(p, q, g, K, QBAR, GSEED, G, E, E2, psi, r, nonces, fmt="minimal")
+    E2b, nb = rows_of(E2), be_rows(nonces, 32)
+    group.hash_format = "minimal"
+    try:
+        pr = S.prove(group, K, QBAR, GSEED, Gb, rows, E2b, np.array(psi, np.uint32), nonce_rows(r), nb)
+        verdict = S.verify(group, K, QBAR, GSEED, Gb, rows, E2b, pr, check_inputs=True)
+        bad = pr.c.copy()
+        bad[31] ^= 0xFF
+        tampered = S.verify(group, K, QBAR, GSEED, Gb, rows, E2b, S.ShuffleProof(**{**vars(pr), "c": bad}))
+    finally:
+        group.hash_format = "fixed"
+    got = pr.to_ints()
+    for name in ("c", "s", "s_hat", "s_prime"):
+        assert getattr(got, name) == getattr(want, name), name
+    assert np.array_equal(pr.pc, be_rows(want.pc, 512)) and np.array_equal(pr.chain, be_rows(want.chain, 512))
+    assert verdict == (True, 0)
+    assert R.CHALLENGE == 4 and not tampered[0] and tampered[1] & R.CHALLENGE
+
+
 def test_proof_across_levels(group):
     """N = 65,537, w = 1: the scan and the tree have a third level (256-way levels).  Generators
     derived on the GPU; verify is true; chain rows at the boundary and at N - 1 by CPython's recurrence."""
