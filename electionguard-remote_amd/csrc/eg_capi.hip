@@ -39,6 +39,7 @@
 #include "../../include/eg_hip_prodpow.h"
 #include "../../include/eg_hip_decrypt2.h"
 #include "../../include/eg_hip_shuffle.h"
+#include "../../include/eg_hip_decode.h"
 #include "eg_kernels.hpp"
 #include "eg_proof_kernels.hpp"
 #include "eg_codes.hpp"
@@ -50,6 +51,7 @@
 #include "eg_prodpow.hpp"
 #include "eg_decrypt2.hpp"
 #include "eg_shuffle.hpp"
+#include "eg_decode.hpp"
 #include "eg_pow16.h"
 #include "eg_stage.hpp"
 
@@ -201,7 +203,12 @@ enum Slot {
   // imported and derived elements
   W_SH_CONST, W_SH_X, W_SH_E, W_SH_O, W_SH_SC, W_SH_JOBS, W_SH_PSI,
   W_SH_R, W_SH_PSI2, W_SH_H, W_SH_D, W_SH_T, W_SH_O2, W_SH_O3, W_SH_TX, W_SH_BE, W_SH_BE2, W_SH_IO, W_SH_LT, W_SH_V,
-  W_SH_W, W_NSLOT
+  W_SH_W,
+  // eg_capi_decode.inc's own: the inverse's exponent p - 2, a host call's rows (twice) and counts, the
+  // elements being inverted, their zero flags and prefix products, the lower levels' elements and prefix
+  // products, the a^(p-2) results, the job table, the texts being decoded
+  W_DC_CONST, W_DC_BE, W_DC_BE2, W_DC_CNT, W_DC_X, W_DC_Z, W_DC_P, W_DC_LV, W_DC_O, W_DC_JOBS, W_DC_Y,
+  W_NSLOT
 };
 
 struct eg_ctx {
@@ -1333,6 +1340,7 @@ extern "C" int eg_ctx_profile_end(eg_ctx* c, double* ms, double* mm, double* sqr
 #include "eg_capi_prodpow.inc"
 #include "eg_capi_decrypt2.inc"
 #include "eg_capi_shuffle.inc"
+#include "eg_capi_decode.inc"
 
 // ------------------------------------------------------------------------------
 // device-pointer powP / fixed-base powP (asynchronous on the ctx stream): the

@@ -105,6 +105,14 @@ EXPORTED_SHUFFLE = [
     "eg_shuffle_verify", "eg_shuffle_verify_dev",
 ]
 
+# Every symbol declared in include/eg_hip_decode.h (decoding decrypted texts: batch inverse and dLog on the device).
+EXPORTED_DECODE = [
+    "eg_batch_inverse", "eg_batch_inverse_dev",
+    "eg_decode_table_create", "eg_decode_table_destroy",
+    "eg_decode_counts", "eg_decode_counts_dev",
+    "eg_decode_plan",
+]
+
 
 class NativeUnavailable(RuntimeError):
     pass
@@ -180,6 +188,9 @@ def _sig(lib: ctypes.CDLL) -> None:
         "eg_prod_pow_plan": ([S, S, I, I, ctypes.POINTER(I), ctypes.POINTER(I), D], I),
         "eg_decrypt2_commit": ([P, P, P, P, S, P, P, P], I),
         "eg_decrypt2_respond": ([P, P, P, P, S, P], I),
+        "eg_decode_table_create": ([P, ctypes.c_uint64, I, ctypes.POINTER(c_vp)], I),
+        "eg_decode_table_destroy": ([P], I),
+        "eg_decode_plan": ([S, ctypes.c_uint64, U32P, U32P, U32P, U32P, U32P, D, D, D], I),
     }
     # declared once, bound twice: name takes host pointers, name_dev device pointers
     pairs = {
@@ -212,6 +223,8 @@ def _sig(lib: ctypes.CDLL) -> None:
         "eg_shuffle_mix": ([P, P, S, S, P, P, P, P], I),
         "eg_shuffle_prove": ([P, P, P, P, S, S] + [P] * 12, I),
         "eg_shuffle_verify": ([P, P, P, P, S, S] + [P] * 9 + [I, P, P], I),
+        "eg_batch_inverse": ([P, P, P, S], I),
+        "eg_decode_counts": ([P, P, P, S, P], I),
     }
     sigs.update({name + dev: sig for name, sig in pairs.items() for dev in ("", "_dev")})
     for name, (args, res) in sigs.items():

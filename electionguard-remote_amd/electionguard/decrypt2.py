@@ -31,6 +31,7 @@ from .core import native
 from .core.group import as_p_array, as_q_array, p_bytes
 from .core.hashing import hash_elems
 from .core.marshal import Columns, be32, be_int, call as _call, ptr
+from .decode import decode_counts
 from .decrypt import _concurrently, _nonces, _texts_array, dlog_g_batch, lagrange, spoiled_texts
 from .keyceremony import GuardianKeys, poly_eval
 
@@ -38,6 +39,7 @@ TAG = 0x30
 MAX_GUARDIANS = 64
 MAX_ITEMS = 1 << 24
 CHUNK_JOBS = 1 << 16   # EG_DECRYPT2_CHUNK_JOBS: exponentiation jobs per chunk of the library's calls
+DECODES = ("host", "device")   # where decrypt_record takes the dLog of B / M
 
 
 def chunk_texts(k: int = 1) -> int:
@@ -310,17 +312,25 @@ class Decryption2:
         shares, comm, M, c, ci, vi = self.rounds(T)
         return M, self.checked(T, shares, comm, c, ci, vi)
 
-    def decrypt_record(self, tally, max_count: int) -> DecryptionRecord2:
+    def decrypt_record(self, tally, max_count: int, decode: str = "host") -> DecryptionRecord2:
+        """decode: "host" takes t = dLog_g(B / M) through multInv_batch, multP_batch and the host's
+        baby-step giant-step; "device" through decode.decode_counts (inverse, table and giant steps on
+        the GPU).  The counts are the same list either way: None where there is no t <= max_count."""
+        if decode not in DECODES:
+            raise ValueError(f"decode: one of {DECODES}, got {decode!r}")
         G = self.group
         T = _texts_array(tally)
         M, proofs = self._combined(T)
         counts = []
-        if len(T):
+        if len(T) and decode == "device":
+            t = decode_counts(G, np.ascontiguousarray(T[:, 1]), M, max_count)
+            counts = [None if c < 0 else int(c) for c in t]
+        elif len(T):
             counts = dlog_g_batch(G, G.multP_batch(np.ascontiguousarray(T[:, 1]), G.multInv_batch(M)), max_count)
         return DecryptionRecord2(T, {t.id(): t.xCoordinate() for t in self.trustees}, M, proofs, counts)
 
-    def decrypt(self, tally, max_count: int) -> List[Optional[int]]:
-        return self.decrypt_record(tally, max_count).counts
+    def decrypt(self, tally, max_count: int, decode: str = "host") -> List[Optional[int]]:
+        return self.decrypt_record(tally, max_count, decode).counts
 
     # ---- spoiled ballots ----
     @staticmethod
@@ -333,14 +343,14 @@ class Decryption2:
             return np.ascontiguousarray(cts).reshape(-1, 2, 512), int(man.NS), int(man.olimit.max())
         return spoiled_texts(man, cts), int(man.n_real), int(man.max_votes_allowed)
 
-    def decrypt_ballots_record(self, ballots, man) -> DecryptionRecord2:
+    def decrypt_ballots_record(self, ballots, man, decode: str = "host") -> DecryptionRecord2:
         T, _, limit = self._ballot_texts(ballots, man)
-        return self.decrypt_record(T, limit)
+        return self.decrypt_record(T, limit, decode)
 
-    def decryptBallots(self, ballots, man) -> np.ndarray:
+    def decryptBallots(self, ballots, man, decode: str = "host") -> np.ndarray:
         """-> (nb, selections) plaintext selections; -1 where a value is not a valid count."""
         T, per, limit = self._ballot_texts(ballots, man)
-        counts = self.decrypt_record(T, limit).counts
+        counts = self.decrypt_record(T, limit, decode).counts
         return np.array([-1 if c is None else int(c) for c in counts], dtype=np.int64).reshape(-1, per)
 
     # ---- contest data ----
